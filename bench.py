@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the Bitmessage double-SHA-512 PoW hot path on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the
+headline figure does not need: the CPU baselines (cpu_baseline), the min-trial proof of a sample of
+the answers (exact_sample), the verify leg's host-buffer runs and hashlib spot-check, and the N > 1
+nonce-sharded leg.  --dump-outputs DIR writes what the last timed step returned (C2: every object's
+nonce, trial value and done code) as DIR/<name>.npy in float64; the inputs are seeded, so two builds
+can be compared output for output.
 
 Default workload (N=1): BASELINE config C2 -- a batch of 1,024 pending msg objects,
 payload sizes L ~ U[512, 16384] drawn with payloads from random.Random(20250216 + rank),
@@ -159,6 +166,31 @@ def solve_batch(lib, h, budget=0):
     pending = 1
     while pending > 0:
         pending = _lib.check(lib, lib.bmpow_batch_step(h, budget), 'bmpow_batch_step')
+
+
+def pair_outputs(res):
+    """The [trial, nonce] pairs a run()/run_batch()/service step returned, as --dump-outputs arrays."""
+    return {'trial': [t for t, _ in res], 'nonce': [n for _, n in res]}
+
+
+#: --dump-outputs writes at most this many values in all (float64: 64 MB)
+DUMP_MAX_VALUES = 8 * 1024 * 1024
+
+
+def dump_outputs(path, outputs, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller, one <name>.npy per array, as
+    float64 (nonces, trial values below the targets and POW values of these workloads are under 2^53,
+    so the conversion is exact for them).  An output set above DUMP_MAX_VALUES is cut to a seeded sample
+    of each array (the same indices in every run).  With several ranks each writes rank<r>_<name>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v).astype(np.float64).ravel() for k, v in outputs.items()}
+    total = sum(a.size for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_MAX_VALUES:
+            keep = max(1, a.size * DUMP_MAX_VALUES // total)
+            a = a[np.sort(np.random.RandomState(SEED).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, ('rank%d_' % rank if world > 1 else '') + name + '.npy'), a)
 
 
 class Claimer(object):
@@ -346,7 +378,8 @@ def run_batch_bench(args, dist):
     exact = None if args.no_exact else prove_sample(lib, objs, nonce, idx, 1000 if args.config == 'c5' else 64,
                                                    SEED + dist.rank)
     return {'desc': desc, 'objects': len(idx) * args.steps, 'useful': useful, 'elapsed': elapsed, 'stats': st,
-            'nonces_sum': int(sum(int(nonce[i]) for i in idx)), 'host_cpu': host_cpu, 'exact_sample': exact}
+            'nonces_sum': int(sum(int(nonce[i]) for i in idx)), 'host_cpu': host_cpu, 'exact_sample': exact,
+            'outputs': {'index': idx, 'nonce': nonce[idx], 'trial': trial[idx], 'done': done[idx]}}
 
 
 def run_service_bench(args, dist):
@@ -394,7 +427,7 @@ def run_service_bench(args, dist):
                                                    1000 if args.config == 'c5' else 64, SEED + dist.rank)
     return {'desc': desc + ' via worker.PowService (native stepping thread)', 'objects': len(objs) * args.steps,
             'useful': useful, 'elapsed': elapsed, 'stats': st,
-            'host_cpu': host_cpu, 'exact_sample': exact}
+            'host_cpu': host_cpu, 'exact_sample': exact, 'outputs': pair_outputs(res)}
 
 
 def run_runbatch_bench(args, dist):
@@ -420,7 +453,7 @@ def run_runbatch_bench(args, dist):
     useful = float(sum(n for _, n in res)) * args.steps
     return {'desc': desc + ' via proofofwork.run_batch', 'objects': len(objs) * args.steps,
             'useful': useful, 'elapsed': elapsed, 'stats': st,
-            'host_cpu': host_cpu}
+            'host_cpu': host_cpu, 'outputs': pair_outputs(res)}
 
 
 def run_serial_bench(args, dist):
@@ -448,7 +481,8 @@ def run_serial_bench(args, dist):
     exact = None if args.no_exact else prove_sample(lib, objs, nonce, list(range(len(objs))), 64, SEED + dist.rank)
     return {'desc': desc + ', one proofofwork.run call after another', 'objects': len(objs) * args.steps,
             'useful': float(sum(nonce)) * args.steps, 'elapsed': elapsed, 'stats': st, 'host_cpu': host_cpu,
-            'exact_sample': exact, 'path': one_path_desc(args, lib), 'call_ms': round(elapsed * 1e3 / len(objs) / args.steps, 3),
+            'exact_sample': exact, 'outputs': pair_outputs(res),
+            'path': one_path_desc(args, lib), 'call_ms': round(elapsed * 1e3 / len(objs) / args.steps, 3),
             'kernel': 'bm_search1_kernel' if single_object_path(args) else 'bm_search_kernel'}
 
 
@@ -483,6 +517,7 @@ def run_c3_bench(args, dist):
     desc = 'C3: fixed initialHash, target=0, 2^%d nonces split over %d GPU(s)' % (args.c3_log2, dist.world)
     return {'desc': desc, 'objects': 0, 'useful': float(share) * args.steps, 'elapsed': elapsed, 'stats': st,
             'scaling': 'strong', 'host_cpu': host_cpu, 'path': one_path_desc(args, lib),
+            'outputs': {'found': [_lib.NOT_FOUND], 'nonce': [n.value], 'trial': [t.value]},  # (sweep asserts it)
             'kernel': 'bm_search1_kernel' if single_object_path(args) else 'bm_search_kernel'}
 
 
@@ -549,6 +584,7 @@ def run_c1_bench(args, dist):
     return {'desc': 'C1: one 1 KB msg at defaults via proofofwork.run (golden nonce 10909138)',
             'objects': args.steps, 'useful': float(nonce) * args.steps, 'elapsed': elapsed, 'stats': st,
             'host_cpu': host_cpu, 'call_ms': round(elapsed * 1e3 / args.steps, 4),
+            'outputs': pair_outputs([[tv, nonce]]),
             'per_call': {'ms': dist(per_ms, 4), 'trials': dist(per_trials, 0),
                          'past_answer_frac': dist([(x - nonce) / x for x in per_trials], 5),
                          'calls_by_past_answer': {k: sum(1 for x in per_trials if lo <= (x - nonce) / x < hi)
@@ -580,9 +616,10 @@ def run_verify_bench(args, dist):
     payload_bytes = sum(len(o) - 8 for o in objs)
     lib = _lib.get()
     with verify.VerifyBatch(objs) as vb:
-        first = vb.run()
-        for i in range(0, n, max(1, n // 500)):  # spot-check against hashlib
-            assert int(first[i]) == targets.pow_value(objs[i]), i
+        if args.full:
+            first = vb.run()
+            for i in range(0, n, max(1, n // 500)):  # spot-check against hashlib
+                assert int(first[i]) == targets.pow_value(objs[i]), i
         for _ in range(args.warmup):
             vb.run(want=False)
         dist.barrier()
@@ -592,8 +629,17 @@ def run_verify_bench(args, dist):
             vb.run(want=False)
         dist.barrier()
         elapsed = time.perf_counter() - t0
-    st = _lib.BmpowStats()
-    lib.bmpow_get_stats(ctypes.byref(st))
+        st = _lib.BmpowStats()
+        lib.bmpow_get_stats(ctypes.byref(st))
+        # the timed passes leave their POW values on the device (want=False): one more pass over the
+        # same resident flood brings them to the host for --dump-outputs
+        outputs = {'pow_value': vb.run()} if args.dump_outputs else None
+    r = {'desc': 'verify: %d received objects (50%% acks, 25%% pubkeys, 25%% msgs 0.5-16 KB), POW of each '
+                 '(protocol.isProofOfWorkSufficient hashing) resident in HBM' % n,
+         'objects': n * args.steps, 'elapsed': elapsed, 'stats': st, 'payload_bytes': payload_bytes * args.steps,
+         'outputs': outputs}
+    if not args.full:
+        return r
     # end to end, the way a caller uses it: host buffers in, verdicts out (padding and sorting on
     # the host, PCIe upload, kernel, IEEE-double verdicts) -- reported beside, never as `value`
     # (first call: allocates the library's staging and device buffers; later floods reuse them)
@@ -611,11 +657,9 @@ def run_verify_bench(args, dist):
                                           - s2.verify_host_verdict_ms, 2)})
         assert len(ok) == n
     best = 1 + min(range(2), key=lambda i: e2e[1 + i])
-    return {'e2e_objects_per_s': n / e2e[best], 'e2e_s': e2e[best], 'e2e_first_s': e2e[0], 'e2e_parts': parts[best],
-            'e2e_fast_marshalling': verify._fast() is not None,
-            'desc': 'verify: %d received objects (50%% acks, 25%% pubkeys, 25%% msgs 0.5-16 KB), POW of each '
-                    '(protocol.isProofOfWorkSufficient hashing) resident in HBM' % n,
-            'objects': n * args.steps, 'elapsed': elapsed, 'stats': st, 'payload_bytes': payload_bytes * args.steps}
+    r.update({'e2e_objects_per_s': n / e2e[best], 'e2e_s': e2e[best], 'e2e_first_s': e2e[0], 'e2e_parts': parts[best],
+              'e2e_fast_marshalling': verify._fast() is not None})
+    return r
 
 
 def summarize_verify(args, dist, r, lib_version):
@@ -630,13 +674,15 @@ def summarize_verify(args, dist, r, lib_version):
         'scaling': 'weak', 'vs_baseline': None, 'dtype': 'u64', 'data': 'synthetic',
         'config': {'workload': r['desc'], 'parallelism': 'object-sharded dp%d' % dist.world, 'lib': lib_version},
         'payload_GBps': round(nbytes / el_max / 1e9, 3),
-        'e2e_host_buffers': {'objects_per_s': round(r['e2e_objects_per_s'], 1), 'seconds': round(r['e2e_s'], 3),
-                             'first_call_seconds': round(r['e2e_first_s'], 3), 'parts': r['e2e_parts'],
-                             'c_marshalling': r['e2e_fast_marshalling'],
-                             'what': 'bmpow_verify_batch_ptrs from host buffers: sort + pad into pinned staging '
-                                     'overlapped with the PCIe upload + kernel + verdicts (rank 0; best of 2 '
-                                     'calls after the first, which allocates the reused buffers)'},
     }
+    if 'e2e_s' in r:  # (--full)
+        line['e2e_host_buffers'] = {
+            'objects_per_s': round(r['e2e_objects_per_s'], 1), 'seconds': round(r['e2e_s'], 3),
+            'first_call_seconds': round(r['e2e_first_s'], 3), 'parts': r['e2e_parts'],
+            'c_marshalling': r['e2e_fast_marshalling'],
+            'what': 'bmpow_verify_batch_ptrs from host buffers: sort + pad into pinned staging '
+                    'overlapped with the PCIe upload + kernel + verdicts (rank 0; best of 2 '
+                    'calls after the first, which allocates the reused buffers)'}
     if st.verify_kernel_ms > 0:
         # algorithmic ops: 4,144 per 128-B payload block (SURVEY 8(d) per-block count) + 8,288 for
         # the outer double hash of each object
@@ -764,7 +810,7 @@ def run_addr_bench(args, dist):
     comb = lib.bmpow_addr_last_comb()
     return {'desc': 'addrgen: %s, found k=%d, %d-bit comb' % (what, k, comb),
             'tries': float(k + 1) * args.steps, 'elapsed': elapsed, 'stats': st, 'k': k,
-            'comb_bits': comb, 'table_build_s': table_s}
+            'comb_bits': comb, 'table_build_s': table_s, 'outputs': {'k': [k], 'ripe': list(bytes(ripe))}}
 
 
 def summarize_addr(args, dist, r, lib_version):
@@ -994,6 +1040,12 @@ def main():
                          'serial call sites), not as one batch')
     ap.add_argument('--throttle', default=None,
                     help='--devices A/B: "shard:ms" -- that shard\'s stepper sleeps ms before each launch')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the CPU baselines, the min-trial proof '
+                         'of a sample of the answers, verify\'s host-buffer legs and hashlib spot-check, and '
+                         'N > 1\'s nonce-sharded leg (each can still be switched off by its own --no-... option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned as DIR/<name>.npy (float64)')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--nonce-sharded-child', type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -1005,6 +1057,10 @@ def main():
         from pybitmessage_amd import _lib
         print(json.dumps(nonce_sharded(_lib.get(), args.nonce_sharded_child, args.share_device)), flush=True)
         return
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_exact = args.no_nonce_sharded = True
 
     dist = Dist()
     # one process per GPU; --share-device puts every rank on GPU 0 (rehearsing the multi-rank
@@ -1029,6 +1085,8 @@ def main():
 
     if args.config == 'addrgen':
         r = run_addr_bench(args, dist)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r['outputs'], dist.rank, dist.world)
         line = summarize_addr(args, dist, r, lib.bmpow_version().decode())
         if dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_addr_baseline(min(args.cpu_seconds, 10.0), args.addr_mode)
@@ -1038,6 +1096,8 @@ def main():
         return
     if args.config == 'verify':
         r = run_verify_bench(args, dist)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r['outputs'], dist.rank, dist.world)
         line = summarize_verify(args, dist, r, lib.bmpow_version().decode())
         if dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_verify_baseline(min(args.cpu_seconds, 10.0))
@@ -1060,6 +1120,8 @@ def main():
         if n != args.devices * args.shards_per_device:
             raise SystemExit('asked for %d shards, the library selected %d' % (args.devices * args.shards_per_device, n))
     r = runner(args, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r['outputs'], dist.rank, dist.world)
     r['devices'] = args.devices
     r['pci_bus_id'] = device_pci_bus_id(lib)
     line = summarize(args, dist, r, lib.bmpow_version().decode())

@@ -22,7 +22,7 @@ for vv in "$@"; do
       c5) args=(--config c5 --objects 4096 --steps 1 --warmup 0) ;;
       c5tm) args=(--config c5 --test-mode --steps 1 --warmup 1) ;;
     esac
-    env BMPOW_LIB=$L "${envs[@]}" timeout -k 10 200 python3 bench.py "${args[@]}" --no-cpu-baseline > "$OUT/${c}_$n.json"
+    env BMPOW_LIB=$L "${envs[@]}" timeout -k 10 200 python3 bench.py --full "${args[@]}" --no-cpu-baseline > "$OUT/${c}_$n.json"
     line="$line $(python3 -c "import json;d=json.load(open('$OUT/${c}_$n.json'));r=d['roofline'];print('$c', d['value'], r['kernel_ghs'])")"
   done
   echo "$line"

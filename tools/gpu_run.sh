@@ -91,32 +91,32 @@ for step in "$@"; do
       n=0; while [ -e "$OUT/${cfg}_serial_${m}_$n.json" ]; do n=$((n + 1)); done
       BMPOW_WAIT1=$m timeout -k 10 300 python3 bench.py --config "$cfg" --serial --steps 1 --warmup 2 --no-cpu-baseline --no-exact \
         > "$OUT/${cfg}_serial_${m}_$n.json" 2> "$OUT/${cfg}_serial_${m}_$n.err" ;;
-    c4-serial) timeout -k 10 300 python3 bench.py --config c4 --serial --objects 8 --steps 1 --warmup 1 --no-cpu-baseline \
+    c4-serial) timeout -k 10 300 python3 bench.py --full --config c4 --serial --objects 8 --steps 1 --warmup 1 --no-cpu-baseline \
         > "$OUT/c4_serial.json" 2> "$OUT/c4_serial.err" ;;
     c1c3-ab:*) timeout -k 10 900 bash tools/cmp_c1.sh "$OUT/c1c3_ab" $(echo "${step#c1c3-ab:}" | tr ',' ' ') \
         > "$OUT/c1c3_ab.txt" 2> "$OUT/c1c3_ab.err" ;;
     c2-wait:*) m=${step#c2-wait:}
-      BMPOW_WAIT=$m timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c2_wait_$m.json" 2> "$OUT/c2_wait_$m.err" ;;
+      BMPOW_WAIT=$m timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c2_wait_$m.json" 2> "$OUT/c2_wait_$m.err" ;;
     devices:*) IFS=: read -r _ n k t <<< "$step"; t=${t:-0}; tag="n${n}_k${k}_t${t}"
       thr=(); [ "$t" = 0 ] || thr=(--throttle "0:$t")
       timeout -k 10 300 python3 bench.py --config c3 --c3-log2 36 --steps 1 --warmup 0 --no-cpu-baseline --devices "$n" \
         --shards-per-device "$k" "${thr[@]}" > "$OUT/c3_dev_$tag.json" 2> "$OUT/c3_dev_$tag.err" &&
-      timeout -k 10 300 python3 bench.py --config c4 --steps 1 --warmup 0 --no-cpu-baseline --devices "$n" \
+      timeout -k 10 300 python3 bench.py --full --config c4 --steps 1 --warmup 0 --no-cpu-baseline --devices "$n" \
         --shards-per-device "$k" "${thr[@]}" > "$OUT/c4_dev_$tag.json" 2> "$OUT/c4_dev_$tag.err" ;;
-    bench) timeout -k 10 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench) timeout -k 10 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     smoke) timeout -k 10 300 python3 -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/smoke.log" 2>&1 ;;
-    bench-quick) timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c2.json" 2> "$OUT/c2.err" ;;
+    bench-quick) timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c2.json" 2> "$OUT/c2.err" ;;
     c1) timeout -k 10 200 python3 bench.py --config c1 --steps 20 --warmup 2 --no-cpu-baseline > "$OUT/c1.json" 2> "$OUT/c1.err" ;;
     c3) timeout -k 10 200 python3 bench.py --config c3 --c3-log2 36 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c3.json" 2> "$OUT/c3.err" ;;
-    c4) timeout -k 10 300 python3 bench.py --config c4 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c4.json" 2> "$OUT/c4.err" ;;
-    c5) timeout -k 10 300 python3 bench.py --config c5 --objects 4096 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c5.json" 2> "$OUT/c5.err" ;;
-    c5-full) timeout -k 10 700 python3 bench.py --config c5 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c5_full_default.json" 2> "$OUT/c5_full_default.err" ;;
-    c5-full-service) timeout -k 10 700 python3 bench.py --config c5 --service --objects 100000 --steps 1 --warmup 0 --no-cpu-baseline \
+    c4) timeout -k 10 300 python3 bench.py --full --config c4 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c4.json" 2> "$OUT/c4.err" ;;
+    c5) timeout -k 10 300 python3 bench.py --full --config c5 --objects 4096 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c5.json" 2> "$OUT/c5.err" ;;
+    c5-full) timeout -k 10 700 python3 bench.py --full --config c5 --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/c5_full_default.json" 2> "$OUT/c5_full_default.err" ;;
+    c5-full-service) timeout -k 10 700 python3 bench.py --full --config c5 --service --objects 100000 --steps 1 --warmup 0 --no-cpu-baseline \
                        > "$OUT/c5_full_default_service.json" 2> "$OUT/c5_full_default_service.err" ;;
-    verify) timeout -k 10 300 python3 bench.py --config verify --no-cpu-baseline > "$OUT/verify.json" 2> "$OUT/verify.err" ;;
+    verify) timeout -k 10 300 python3 bench.py --full --config verify --no-cpu-baseline > "$OUT/verify.json" 2> "$OUT/verify.err" ;;
     addrgen) timeout -k 10 300 python3 bench.py --config addrgen --no-cpu-baseline > "$OUT/addrgen.json" 2> "$OUT/addrgen.err" ;;
     rocprof-bench) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -o run -- \
-                     python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/rocprof_bench.json" 2> "$OUT/rocprof_bench.err" ;;
+                     python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/rocprof_bench.json" 2> "$OUT/rocprof_bench.err" ;;
     c1-trace) timeout -k 10 300 rocprofv3 --kernel-trace --hip-trace --output-format csv -d "$OUT/c1_trace" -o run -- \
                 python3 bench.py --config c1 --steps 50 --warmup 3 --no-cpu-baseline > "$OUT/c1_trace.json" 2> "$OUT/c1_trace.err" &&
               python3 tools/c1_timeline.py "$OUT/c1_trace" > "$OUT/c1_timeline.json" ;;
@@ -135,7 +135,7 @@ for step in "$@"; do
     ubench-mix) timeout -k 10 300 ./tools/ubench_mix > "$OUT/ubench_mix.jsonl" 2> "$OUT/ubench_mix.err" ;;
     rehearse-n*) n=${step#rehearse-n}
       timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-        --master-port $((29500 + n)) bench.py --gpus "$n" --steps 1 --warmup 1 --share-device \
+        --master-port $((29500 + n)) bench.py --full --gpus "$n" --steps 1 --warmup 1 --share-device \
         > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err" ;;
     ab:*) CONFIGS=${AB_CONFIGS:-c3} timeout -k 10 900 bash tools/cmp_variants.sh "$OUT/ab" $(echo "${step#ab:}" | tr ',' ' ') \
             > "$OUT/ab.txt" 2> "$OUT/ab.err" ;;

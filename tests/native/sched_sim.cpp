@@ -560,7 +560,7 @@ static void scenario_var() {
       if (c.vpool_epoch != ep) ++compactions;
       if (!c.vmoved.empty()) {
         ++moved;
-        vl.init_slots(c, c.vmoved);  // bmpow_host.hip: after the (drained) pool re-upload
+        vl.init_slots(c, c.vmoved);  // bmpow_host_batch.hip: after the (drained) pool re-upload
         c.vmoved.clear();
       }
       vl.init_slots(c, slots);

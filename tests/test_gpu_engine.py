@@ -73,7 +73,7 @@ def test_throttled_shard_does_not_gate_the_others(gpulib, shards, engine_split, 
 def test_steppers_idle_priority_and_cpu(gpulib, shards):
     """Every stepper thread runs at SCHED_IDLE and, while a C2-like batch keeps the GPU busy for a
     few seconds, uses a small share of one CPU (it sleeps between queries of its launch's event,
-    bmpow_host.hip engine_wait)."""
+    bmpow_host_batch.hip engine_wait)."""
     shards([0, 0])
     objs, _ = bench.make_objects('c2', 0, 96)
     cpu0 = (ctypes.c_double * 2)()
@@ -88,7 +88,7 @@ def test_steppers_idle_priority_and_cpu(gpulib, shards):
     gpulib.bmpow_get_thread_info(cpu1, pol, 2)
     per_s = [(b - a) / wall for a, b in zip(cpu0, cpu1)]
     assert wall > 0.3
-    # bound from the wait's schedule (bmpow_host.hip engine_wait): a stepper sleeps max(20 us, min(1 ms,
+    # bound from the wait's schedule (bmpow_host_batch.hip engine_wait): a stepper sleeps max(20 us, min(1 ms,
     # waited / 32)) between event queries -- ~290 wake-ups over a 160 ms launch (half the device), about
     # 1,800 per second -- and a wake-up (event query, nanosleep, reschedule) costs well under 28 us:
     # 1,800 x 28 us = 0.05 s per second.  Measured 0.0045 (profiles/r04/final/bench.json host_cpu).
@@ -311,7 +311,7 @@ def test_long_run_leaves_the_cpu_alone(gpulib, shards):
     wall, used = time.perf_counter() - w0, cpu() - c0
     st = _lib.BmpowStats()
     gpulib.bmpow_get_stats(ctypes.byref(st))
-    # bound from the sleeping wait (bmpow_host.hip wait_one): it sleeps min(250 us, max(20 us, waited /
+    # bound from the sleeping wait (bmpow_host_one.hip wait_one): it sleeps min(250 us, max(20 us, waited /
     # 64)) between polls of the result word -- past the first 16 ms of a window, 4,000 polls per second,
     # each a load of host memory and a nanosleep (with an event query every g_one_query polls), well under
     # 25 us: 4,000 x 25 us = 0.1 s per second.  Measured 0.007 (profiles/r05/final/c3.json host_cpu).

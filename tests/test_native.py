@@ -45,3 +45,20 @@ def test_scheduler_unit_under_sanitizer(flavour):
     assert r.returncode == 0, r.stderr[-4000:]
     assert 'all scenarios passed' in r.stderr
     assert 'WARNING: ThreadSanitizer' not in r.stderr and 'runtime error' not in r.stderr
+
+
+def test_owner_unit_under_sanitizer():
+    """The device-buffer owners (pybitmessage_amd/csrc/bmpow_own.h) over a counting stand-in for the HIP
+    runtime (tests/native/own_sim.cpp), under AddressSanitizer + UBSan with leak detection: a stand-alone
+    program that loads neither HIP nor the library."""
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, 'own_sim_asan_ubsan')
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Werror'] + FLAVOURS['asan_ubsan'] +
+                          [os.path.join(ROOT, 'tests', 'native', 'own_sim.cpp'), '-o', exe])
+    env = dict(os.environ)
+    env['ASAN_OPTIONS'] = 'halt_on_error=1 detect_leaks=1'
+    env['UBSAN_OPTIONS'] = 'halt_on_error=1 print_stacktrace=1'
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert 'all owner checks passed' in r.stderr
+    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr

@@ -4,7 +4,7 @@
     rocprofv3 --kernel-trace --hip-trace --output-format csv -d D -o run -- python3 bench.py --config c1 ...
     python tools/c1_timeline.py D > timeline.json
 
-Each call of the single-object path (bmpow_host.hip search_one) launches bm_search1_kernel once per
+Each call of the single-object path (bmpow_host_one.hip search_one) launches bm_search1_kernel once per
 piece and window (one device: one launch per window; a split call: one per piece), in a burst; a launch
 more than 200 us after the previous launch call returned starts a new call.  Per call:
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fixed cost of one single-object launch (bmpow_host.hip search_one, bm_search1_kernel): windows
+"""Fixed cost of one single-object launch (bmpow_host_one.hip search_one, bm_search1_kernel): windows
 of N nonces with no hit (target 0), N = 2^20 .. 2^27, 20 calls each; per call the wall time and the
 kernel's own span (s_memrealtime, bmpow_stats.kernel_ms).  A least-squares line t = a + N / rate gives
 the per-launch fixed cost a (launch, ramp, last partial row) and the streaming rate.

@@ -143,8 +143,28 @@ SIGNATURES = [
     ('BitmessagePOW', ctypes.c_ulonglong, [ctypes.c_char_p, ctypes.c_ulonglong]),
 ]
 
+
+class BmpowEciesStats(ctypes.Structure):
+    """``bmpow_ecies_stats`` (include/bmpow_ecies.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('objects', ctypes.c_uint64), ('pairs', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('prep_ms', ctypes.c_double), ('ecdh_ms', ctypes.c_double),
+                ('mac_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_ecies.h declares
+ECIES_SIGNATURES = [
+    ('bmpow_ecdh', ctypes.c_int, [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, _pu8, _pu8]),
+    ('bmpow_ecies_parse', ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, _pu8, ctypes.POINTER(ctypes.c_size_t)]),
+    ('bmpow_ecies_match', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), _pu8]),
+    ('bmpow_ecies_decrypt', ctypes.c_int64, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, _pu8, ctypes.c_size_t]),
+    ('bmpow_ecies_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowEciesStats)]),
+    ('bmpow_ecies_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
+_host = None
 _exit_hooked = False
 
 
@@ -159,7 +179,7 @@ def load(path=None):
         raise BmpowUnavailable(E_NODEV, 'libbmpow_hip.so not built at %s (run __graft_entry__.build() '
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
-    for name, res, args in SIGNATURES:
+    for name, res, args in SIGNATURES + ECIES_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -188,6 +208,18 @@ def get():
                 atexit.register(_at_exit, lib)
                 _exit_hooked = True
         return _lib
+
+
+def host():
+    """The library for its host-only entry points (``bmpow_ecies_parse``, ``bmpow_ecies_decrypt``, ...):
+    the initialised handle when there is one, else a handle loaded without touching a device."""
+    global _host
+    with _lock:
+        if _lib is not None:
+            return _lib
+        if _host is None:
+            _host = load()
+        return _host
 
 
 def _at_exit(lib):

@@ -22,6 +22,7 @@
 //   bmpow_host_batch.hip   batch tables, the engine's device side, min-trial probe, searches, the service
 //   bmpow_host_one.hip     run()'s single-object path and the streams kept for it
 //   bmpow_host_verify.hip  receive-side verification;   bmpow_host_addr.hip  the address search
+//   bmpow_host_ecies.hip   ECIES trial decryption of received msgs (include/bmpow_ecies.h)
 #include "bmpow_host.h"
 
 namespace bmhost {

@@ -162,6 +162,40 @@ ECIES_SIGNATURES = [
     ('bmpow_ecies_reset_stats', None, []),
 ]
 
+
+class BmpowIntakeStats(ctypes.Structure):
+    """``bmpow_intake_stats`` (include/bmpow_intake.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('objects', ctypes.c_uint64), ('blocks', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('kernel_ms', ctypes.c_double), ('host_build_ms', ctypes.c_double),
+                ('host_run_ms', ctypes.c_double), ('host_status_ms', ctypes.c_double)]
+
+
+class BmpowIntakeRec(ctypes.Structure):
+    """``bmpow_intake_rec`` (include/bmpow_intake.h): one object's header fields, hash, POW value and status."""
+    _fields_ = [('nonce', ctypes.c_uint64), ('expires', ctypes.c_uint64), ('version', ctypes.c_uint64),
+                ('stream', ctypes.c_uint64), ('pow', ctypes.c_uint64), ('object_type', ctypes.c_uint32),
+                ('payload_offset', ctypes.c_uint32), ('status', ctypes.c_int32), ('reserved', ctypes.c_uint32),
+                ('inv', ctypes.c_uint8 * 32)]
+
+
+class BmpowIntakeParams(ctypes.Structure):
+    """``bmpow_intake_params`` (include/bmpow_intake.h)."""
+    _fields_ = [('now', ctypes.c_int64), ('recv_time', ctypes.c_int64), ('ntpb', ctypes.c_uint64),
+                ('extra', ctypes.c_uint64), ('streams', _p64), ('n_streams', ctypes.c_size_t)]
+
+
+# the same for every symbol include/bmpow_intake.h declares
+INTAKE_SIGNATURES = [
+    ('bmpow_inventory_hashes', ctypes.c_int, [ctypes.c_size_t, ctypes.c_void_p, _p64, _pu8]),
+    ('bmpow_intake_header', ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(BmpowIntakeRec)]),
+    ('bmpow_intake_status', ctypes.c_int,
+     [ctypes.POINTER(BmpowIntakeRec), ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, _p64, ctypes.c_size_t]),
+    ('bmpow_intake_batch', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.POINTER(BmpowIntakeParams), ctypes.c_void_p]),
+    ('bmpow_intake_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowIntakeStats)]),
+    ('bmpow_intake_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -179,7 +213,7 @@ def load(path=None):
         raise BmpowUnavailable(E_NODEV, 'libbmpow_hip.so not built at %s (run __graft_entry__.build() '
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
-    for name, res, args in SIGNATURES + ECIES_SIGNATURES:
+    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -199,5 +199,6 @@ void engine_release_shards();
 void probe_release_shards();
 void verify_release_shards();
 void addr_release_shards();
+void intake_release_shards();
 
 }  // namespace bmhost

@@ -23,6 +23,7 @@
 //   bmpow_host_one.hip     run()'s single-object path and the streams kept for it
 //   bmpow_host_verify.hip  receive-side verification;   bmpow_host_addr.hip  the address search
 //   bmpow_host_ecies.hip   ECIES trial decryption of received msgs (include/bmpow_ecies.h)
+//   bmpow_host_intake.hip  object intake: inventory hashes, header walk and checks (include/bmpow_intake.h)
 #include "bmpow_host.h"
 
 namespace bmhost {
@@ -41,6 +42,7 @@ void free_shards() {
   probe_release_shards();
   verify_release_shards();
   addr_release_shards();
+  intake_release_shards();
   for (Shard& s : g_shards) {
     s.ev0.reset();
     s.ev1.reset();

@@ -1,37 +1,6 @@
 // bmpow_host_verify.hip -- receive-side verification: the sessions (bmpow_vbatch_*) and the one-shot
 // entry points (bmpow_pow_values, bmpow_verify_batch*, bmpow_pow_sufficient).
-#include "bmpow_host.h"
-
-// ---------------------------------------------------------------------------------------
-// Receive-side verification session.  Layout per shard, device resident:
-//   pool[blocks]  : every payload (object[8:]) SHA-512-padded to whole 128-B blocks, objects
-//                   back to back in sorted order (so one lane reads one contiguous run)
-//   obj[k]        : {first block, block count, nonce} of the k-th object in sorted order
-//   pow[k]        : result
-// Objects are sorted by block count (descending) so a wave's lanes iterate alike, and the
-// sorted list is cut into per-shard slices of equal block totals.
-// ---------------------------------------------------------------------------------------
-struct bmpow_vbatch {
-  size_t n = 0;
-  struct Part : bmsched::VPart {  // shard, sorted order, bv_obj list, blocks (bmpow_sched.h)
-    bv_obj* d_obj = nullptr;
-    uint4* d_pool = nullptr;
-    uint64_t* d_pow = nullptr;
-    uint64_t* h_pow = nullptr;  // pinned
-    uint32_t* d_bins = nullptr; // plan_bins' offsets + group lists (binned kernel), or null
-    // The pointers above are what the kernels read: a session's own buffers, held here, or (the one-shot
-    // path, these left empty) plain pointers into the shard's buffers (VerifyShard).
-    struct Own {
-      bmown::DevBuf<bv_obj> obj;
-      bmown::DevBuf<uint4> pool;
-      bmown::DevBuf<uint64_t> pow;
-      bmown::PinBuf<uint64_t> h_pow;
-      bmown::DevBuf<uint32_t> bins;
-    } own;
-  };
-  std::vector<Part> parts;
-  uint64_t blocks = 0;
-};
+#include "bmpow_host_vbatch.h"  // struct bmpow_vbatch; vbatch_build / vbatch_release_plan, shared with the intake
 
 namespace bmhost {
 
@@ -140,7 +109,7 @@ void vbatch_release_plan(bmpow_vbatch* vb) {
   for (size_t i = 0; i < vb->parts.size(); ++i) std::swap(static_cast<bmsched::VPart&>(vb->parts[i]), g_vplan[i]);
 }
 
-int vbatch_build(bmpow_vbatch* vb, const std::vector<Span>& objs, bool transient = false) {
+int vbatch_build(bmpow_vbatch* vb, const std::vector<Span>& objs, bool transient) {
   vb->n = objs.size();
   // the plan's vectors live in g_vplan between calls (swapped into the parts here, back by
   // vbatch_release_plan): a flood's descriptors are tens of MB, and fresh pages cost more than

@@ -196,6 +196,25 @@ INTAKE_SIGNATURES = [
     ('bmpow_intake_reset_stats', None, []),
 ]
 
+
+
+class BmpowSigStats(ctypes.Structure):
+    """``bmpow_sig_stats`` (include/bmpow_sig.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('submitted', ctypes.c_uint64), ('uploaded', ctypes.c_uint64),
+                ('ladders', ctypes.c_uint64), ('launches', ctypes.c_uint64), ('hash_ms', ctypes.c_double),
+                ('scalar_ms', ctypes.c_double), ('curve_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_sig.h declares
+SIG_SIGNATURES = [
+    ('bmpow_sig_parse', ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, _pu8]),
+    ('bmpow_ecdsa_verify_digest', ctypes.c_int, [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _pu8]),
+    ('bmpow_sig_verify', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p, _p64, ctypes.c_char_p, _pu8]),
+    ('bmpow_sig_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowSigStats)]),
+    ('bmpow_sig_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -213,7 +232,7 @@ def load(path=None):
         raise BmpowUnavailable(E_NODEV, 'libbmpow_hip.so not built at %s (run __graft_entry__.build() '
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
-    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES:
+    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -194,6 +194,10 @@ int search_one(const uint8_t ih[64], uint64_t target, uint64_t start, uint64_t m
                uint64_t* trial_out, std::unique_lock<FairMutex>& g);
 void one_reset_stats();
 void one_add_stats(size_t shard, uint64_t* trials, double* kernel_ms);
+// bmpow_host_addr.hip: the 16-bit fixed-base comb of the shard's device (table[i << 16 | v] =
+// v 2^(16 i) G, affine), built on first use and kept with the shard set -- the address search's
+// table, shared with the signature verification
+int addr_comb16_table(Shard& sh, const ec::ge** table);
 // Each subsystem's per-shard state, released (bmpow_host.hip free_shards: after the shard's stream drained)
 void engine_release_shards();
 void probe_release_shards();

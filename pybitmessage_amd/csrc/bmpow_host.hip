@@ -24,6 +24,7 @@
 //   bmpow_host_verify.hip  receive-side verification;   bmpow_host_addr.hip  the address search
 //   bmpow_host_ecies.hip   ECIES trial decryption of received msgs (include/bmpow_ecies.h)
 //   bmpow_host_intake.hip  object intake: inventory hashes, header walk and checks (include/bmpow_intake.h)
+//   bmpow_host_sig.hip     ECDSA signature verification of received objects (include/bmpow_sig.h)
 #include "bmpow_host.h"
 
 namespace bmhost {

@@ -52,6 +52,13 @@ int ensure_table(Shard& sh, int c = 0) {
   return 0;
 }
 
+int addr_comb16_table(Shard& sh, const ec::ge** table) {
+  const int rc = ensure_table(sh, 0);
+  if (rc < 0) return rc;
+  *table = comb_table(sh.dev, 0);
+  return 0;
+}
+
 // Comb choice for one search: the 24-bit comb when forced (bmpow_addr_set_comb(24)), or in auto
 // mode when it is already built on every shard or the search is expected to take >= 2^32 tries
 // (4+ null bytes: seconds of work, against ~0.4 s to build the table once per device; judged from

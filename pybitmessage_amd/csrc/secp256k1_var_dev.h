@@ -121,23 +121,31 @@ BM_DEV void var_entry(ge& q, const ge* __restrict__ tab, size_t stride, size_t o
   for (int i = 0; i < 8; ++i) q.y.d[i] = d < 0 ? ny.d[i] : q.y.d[i];
 }
 
-// x(k R), canonical, for the digit string dig[0 .. 64) of k (least significant first) and object o's
-// table; false when k R is the point at infinity (no scalar in [1, n) gives it).
-BM_DEV bool var_mult_x(fe& x, const ge* __restrict__ tab, size_t stride, size_t o, const int32_t* __restrict__ dig) {
+// k R in Jacobian coordinates for the digit string dig[0], dig[dstride], ..., 64 digits of k (least
+// significant first; int32 or int8 each), and object o's table.
+template <class D>
+BM_DEV void var_mult_jac(gej& acc, const ge* __restrict__ tab, size_t stride, size_t o, const D* __restrict__ dig,
+                         size_t dstride) {
   ge q;
-  var_entry(q, tab, stride, o, dig[kVarDigits - 1]);
-  gej acc;
+  var_entry(q, tab, stride, o, dig[(kVarDigits - 1) * dstride]);
   acc.x = q.x;
   acc.y = q.y;
   fe_set(acc.z, 1);
   acc.inf = false;
 #pragma unroll 1
   for (int i = kVarDigits - 2; i >= 0; --i) {
-    var_entry(q, tab, stride, o, dig[i]);  // issued ahead of the four doublings that hide its latency
+    var_entry(q, tab, stride, o, dig[i * dstride]);  // issued ahead of the four doublings that hide its latency
 #pragma unroll 1
     for (int j = 0; j < 4; ++j) gej_double(acc, acc);
     gej_add_ge(acc, acc, q);
   }
+}
+
+// x(k R), canonical, for the digit string dig[0 .. 64) of k (least significant first) and object o's
+// table; false when k R is the point at infinity (no scalar in [1, n) gives it).
+BM_DEV bool var_mult_x(fe& x, const ge* __restrict__ tab, size_t stride, size_t o, const int32_t* __restrict__ dig) {
+  gej acc;
+  var_mult_jac(acc, tab, stride, o, dig, 1);
   if (acc.inf) {
     fe_set(x, 0);
     return false;

@@ -1,0 +1,421 @@
+"""TEST INFRASTRUCTURE ONLY -- exact oracle for the ECDSA verification and the ECDH of secp256k1.
+
+Only ``tests/`` may use it; nothing in ``pybitmessage_amd/`` imports it.
+
+Restates, in pure Python integers, what the reference computes when it checks a signature
+(``highlevelcrypto.verify``, ``src/highlevelcrypto.py:88-108``: ``pyelliptic.ECC.verify`` under SHA-1 and
+then under SHA-256, ``src/pyelliptic/ecc.py:387-440``, OpenSSL's ``ECDSA_verify``) and when it tries a key
+on a received msg (``ECDH_compute_key``, ``src/pyelliptic/ecc.py:243``):
+
+* ``mult_g(k)``, ``mult(k, Q)``, ``on_curve``   -- the group, Jacobian coordinates over Python ints;
+* ``verify_digest(Q, r, s, e)``                -- the textbook equation with the range checks;
+* ``verify(msg, der_sig, key64)``              -- strict DER, SHA-1 then SHA-256, as the code 0 / 1 / 2;
+* ``from_u``, ``from_s``, ``sign``, ``hit_case`` -- constructors: signatures whose scalars u1, u2, s or e
+  are chosen freely, with the verdict known from integers alone;
+* ``comb_trace``                               -- an integer model of the kernel's ``comb_add``
+  (``pybitmessage_amd/csrc/bmpow_sig.hip``): which 16-bit window of u1 meets plus or minus the
+  accumulator, so a test can prove that a constructed case reaches the branch it was built for;
+* ``scalar_set``, ``comb_cases``, ``scalar_cases``, ``hash_cases`` -- the constructed families the CPU and
+  GPU tests share (seeded, built once per process).
+
+Pinned by the reference-made fixtures ``tests/golden/sig_kats.json`` and ``tests/golden/ecies_kats.json``
+and by ``oracle/addrgen_oracle.py`` (``tests/test_ecdsa_oracle.py``) before anything is checked against it.
+A ``mult_g`` costs about 0.1 ms, a ``mult`` about 1.5 ms.
+"""
+import collections
+import functools
+import hashlib
+import random
+
+P = 2 ** 256 - 2 ** 32 - 977
+N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+GX = 0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798
+GY = 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8
+G = (GX, GY)
+
+COMB_BITS = 16   # the kernel's comb: table[i << 16 | v] = v 2^(16 i) G, 16 windows
+COMB_WINDOWS = 16
+
+
+# ------------------------------------------------------------------ the group (y^2 = x^3 + 7)
+# Affine points are (x, y) or None for the point at infinity; Jacobian ones (X, Y, Z) or None.
+def on_curve(pt):
+    """Whether (x, y) has both coordinates below p and lies on the curve."""
+    x, y = pt
+    return 0 <= x < P and 0 <= y < P and (y * y - x * x * x - 7) % P == 0
+
+
+def neg(pt):
+    return None if pt is None else (pt[0], -pt[1] % P)
+
+
+def jac_double(p):
+    if p is None or p[1] == 0:
+        return None
+    x, y, z = p
+    a, b = x * x % P, y * y % P
+    c = b * b % P
+    d = 2 * ((x + b) * (x + b) - a - c) % P
+    e = 3 * a % P
+    x3 = (e * e - 2 * d) % P
+    return x3, (e * (d - x3) - 8 * c) % P, 2 * y * z % P
+
+
+def jac_add_affine(p, q):
+    """p + q for a Jacobian p and an affine q, complete: infinity, doubling and cancellation included."""
+    if q is None:
+        return p
+    if p is None:
+        return q[0], q[1], 1
+    x1, y1, z1 = p
+    zz = z1 * z1 % P
+    h = (q[0] * zz - x1) % P
+    rr = (q[1] * zz * z1 - y1) % P
+    if h == 0:
+        return jac_double(p) if rr == 0 else None
+    hh = h * h % P
+    hhh = h * hh % P
+    v = x1 * hh % P
+    x3 = (rr * rr - hhh - 2 * v) % P
+    return x3, (rr * (v - x3) - y1 * hhh) % P, z1 * h % P
+
+
+def to_affine(p):
+    if p is None:
+        return None
+    zi = pow(p[2], -1, P)
+    zi2 = zi * zi % P
+    return p[0] * zi2 % P, p[1] * zi2 * zi % P
+
+
+def add(p1, p2):
+    """Affine p1 + p2."""
+    return to_affine(jac_add_affine(None if p1 is None else (p1[0], p1[1], 1), p2))
+
+
+def _affine_add(p1, p2):  # table building: both finite, p1 != +-p2
+    lam = (p2[1] - p1[1]) * pow(p2[0] - p1[0], -1, P) % P
+    x3 = (lam * lam - p1[0] - p2[0]) % P
+    return x3, (lam * (p1[0] - x3) - p1[1]) % P
+
+
+_G_BITS = 8
+_g_table = []  # _g_table[i][v] = v 2^(8 i) G, built on first use
+
+
+def _build_g_table():
+    base = G
+    for _ in range(256 // _G_BITS):
+        row = [None, base, to_affine(jac_double((base[0], base[1], 1)))]
+        for _ in range(3, 1 << _G_BITS):
+            row.append(_affine_add(row[-1], base))
+        _g_table.append(row)
+        base = _affine_add(row[-1], base)  # 255 b + b = 2^8 b
+
+
+def mult_g(k):
+    """k G (affine; None for k = 0 mod n), by a fixed-base window table of G."""
+    if not _g_table:
+        _build_g_table()
+    k %= N
+    acc = None
+    for row in _g_table:
+        v = k & 0xFF
+        if v:
+            acc = jac_add_affine(acc, row[v])
+        k >>= _G_BITS
+    return to_affine(acc)
+
+
+def mult(k, pt):
+    """k pt for an affine point of the curve (None for k = 0 mod n or pt = infinity): width-5 NAF over
+    the odd multiples pt, 3 pt, ..., 15 pt."""
+    k %= N
+    if k == 0 or pt is None:
+        return None
+    two = to_affine(jac_double((pt[0], pt[1], 1)))
+    odd = [pt]
+    for _ in range(7):
+        odd.append(_affine_add(odd[-1], two))  # pt has the prime order n: no two of 1..15 pt meet
+    naf = []
+    while k:
+        d = 0
+        if k & 1:
+            d = k & 31
+            if d >= 16:
+                d -= 32
+            k -= d
+        naf.append(d)
+        k >>= 1
+    acc = None
+    for d in reversed(naf):
+        acc = jac_double(acc)
+        if d > 0:
+            acc = jac_add_affine(acc, odd[d >> 1])
+        elif d < 0:
+            acc = jac_add_affine(acc, neg(odd[-d >> 1]))
+    return to_affine(acc)
+
+
+# ------------------------------------------------------------------ verification
+def verify_digest(Q, r, s, e):
+    """The textbook equation, as the reference's ECDSA_verify decides it: 1 <= r, s < n, Q = (x, y) with
+    both coordinates below p and on the curve, e any integer (taken mod n); w = 1 / s, u1 = e w,
+    u2 = r w, R = u1 G + u2 Q; valid iff R is not infinity and x(R) mod n = r."""
+    if not (1 <= r < N and 1 <= s < N) or not on_curve(Q):
+        return False
+    w = pow(s, -1, N)
+    R = add(mult_g(e % N * w % N), mult(r * w % N, Q))
+    return R is not None and R[0] % N == r
+
+
+def der_decode(sig):
+    """Strict decode: (r, s) of a canonical DER SEQUENCE { INTEGER, INTEGER } (short-form lengths, minimal
+    non-negative integers, nothing after), else None."""
+    def integer(b):
+        if len(b) < 2 or b[0] != 2 or b[1] >= 0x80 or b[1] == 0 or len(b) < 2 + b[1]:
+            return None
+        v = b[2:2 + b[1]]
+        if v[0] & 0x80 or (len(v) > 1 and v[0] == 0 and not v[1] & 0x80):
+            return None
+        return int.from_bytes(v, 'big'), b[2 + b[1]:]
+    if len(sig) < 2 or sig[0] != 0x30 or sig[1] >= 0x80 or sig[1] != len(sig) - 2:
+        return None
+    r = integer(sig[2:])
+    s = integer(r[1]) if r else None
+    if not s or s[1]:
+        return None
+    return r[0], s[0]
+
+
+def der_encode(r, s):
+    def integer(v):
+        b = v.to_bytes(max(1, (v.bit_length() + 7) // 8), 'big')
+        if b[0] & 0x80:
+            b = b'\x00' + b
+        return b'\x02' + bytes([len(b)]) + b
+    body = integer(r) + integer(s)
+    return b'\x30' + bytes([len(body)]) + body
+
+
+def key_xy(key64):
+    return int.from_bytes(key64[:32], 'big'), int.from_bytes(key64[32:], 'big')
+
+
+def xy_key(pt):
+    return pt[0].to_bytes(32, 'big') + pt[1].to_bytes(32, 'big')
+
+
+def verify(msg, der_sig, key64):
+    """``highlevelcrypto.verify`` as a code: 1 valid under SHA-1, 2 valid under SHA-256 only, 0 otherwise
+    (a signature that is no canonical DER, r or s out of range, a key that is not 64 bytes, has a
+    coordinate >= p or is off the curve)."""
+    rs = der_decode(bytes(der_sig))
+    if rs is None or len(key64) != 64:
+        return 0
+    Q = key_xy(bytes(key64))
+    for code, alg in ((1, hashlib.sha1), (2, hashlib.sha256)):
+        if verify_digest(Q, rs[0], rs[1], int.from_bytes(alg(msg).digest(), 'big')):
+            return code
+    return 0
+
+
+# ------------------------------------------------------------------ constructors
+Case = collections.namedtuple('Case', 'Q r s e valid')
+
+
+def from_u(u1, u2, d):
+    """The signature whose verification computes exactly u1 G + u2 Q for Q = d G: t = u1 + u2 d, R = t G,
+    r = x(R) mod n, s = r / u2, e = u1 s.  Valid iff t != 0; for t = 0 (R is infinity whatever r is) r is
+    a fixed function of u1 and u2."""
+    u1, u2, d = u1 % N, u2 % N, d % N
+    assert u2 and d
+    t = (u1 + u2 * d) % N
+    r = mult_g(t)[0] % N if t else (u1 + u2 * u2) % N or 1
+    assert r  # x(R) = 0 mod n does not occur for the seeds in use
+    s = r * pow(u2, -1, N) % N
+    return Case(mult_g(d), r, s, u1 * s % N, t != 0)
+
+
+def from_s(k, s, e):
+    """The key that makes (r = x(k G) mod n, s) a valid signature of e: d = (s k - e) / r."""
+    r = mult_g(k)[0] % N
+    assert r
+    d = (s * k - e) * pow(r, -1, N) % N
+    assert d
+    return Case(mult_g(d), r, s % N, e, True)
+
+
+def sign(d, k, e):
+    """Ordinary signing of the digest e with the key d and the nonce k: (r, s)."""
+    r = mult_g(k)[0] % N
+    s = (e + r * d) * pow(k, -1, N) % N
+    assert r and s
+    return r, s
+
+
+def comb_windows(u1):
+    return [(u1 >> (COMB_BITS * i)) & 0xFFFF for i in range(COMB_WINDOWS)]
+
+
+def comb_trace(u1, t0, complete=True):
+    """The kernel's ``comb_add`` over scalars: the accumulator starts as t0 G (t0 = u2 d) and takes the
+    16-bit windows of u1 from the lowest up, zero windows skipped.  Returns (events, outcome): one
+    (window, kind) per non-zero window, kind 'add', 'double' (the accumulator equals the table entry),
+    'cancel' (it equals minus the entry) or 'from_inf' (the accumulator is infinity); outcome the final
+    scalar t (0: infinity).  With ``complete=False`` the addition has no special cases: the trace stops
+    at the first 'double' or 'cancel' with the outcome 'undefined'."""
+    assert 0 <= u1 < N
+    acc, events = t0 % N, []
+    for i, v in enumerate(comb_windows(u1)):
+        if not v:
+            continue
+        m = (v << (COMB_BITS * i)) % N
+        kind = 'from_inf' if acc == 0 else 'double' if acc == m else 'cancel' if acc == N - m else 'add'
+        events.append((i, kind))
+        if not complete and kind in ('double', 'cancel'):
+            return events, 'undefined'
+        acc = (acc + m) % N
+    return events, acc
+
+
+def hit_case(windows, i, kind, u2, off=0):
+    """u1 = sum windows[j] 2^(16 j) and the key d that makes the comb's accumulator meet plus (kind
+    'double') or minus ('cancel') the table entry exactly at window i:
+    u2 d + sum_{j<i} w_j 2^(16 j) = +-w_i 2^(16 i) (+ off, for the sibling that misses by off).
+    Returns (u1, d, from_u(u1, u2, d))."""
+    assert len(windows) == COMB_WINDOWS and windows[i] and kind in ('double', 'cancel')
+    u1 = sum(w << (COMB_BITS * j) for j, w in enumerate(windows))
+    assert u1 < N
+    below = u1 & ((1 << (COMB_BITS * i)) - 1)
+    m = windows[i] << (COMB_BITS * i)
+    d = ((m if kind == 'double' else -m) - below + off) * pow(u2, -1, N) % N
+    return u1, d, from_u(u1, u2, d)
+
+
+# ------------------------------------------------------------------ the constructed families
+def scalar_set():
+    """V: the structured scalars of [1, n) the device arithmetic mod n is driven with."""
+    return list(_scalar_set())
+
+
+@functools.lru_cache(maxsize=None)
+def _scalar_set():
+    rng = random.Random(29)
+    v = [1, 2, 3, N - 1, N - 2, (N + 1) // 2, (N - 1) // 2]
+    for j in range(1, 256, 5):
+        v += [2 ** j, N - 2 ** j]
+    for j in range(1, 64):
+        v += [16 ** j + 1, 16 ** j - 1]
+    for _ in range(200):  # sparse and dense limb patterns (the folds' carry chains)
+        x = 0
+        for i in range(8):
+            x |= rng.choice([0, 0xFFFFFFFF, rng.getrandbits(32)]) << (32 * i)
+        v.append(x % N or 1)
+    v += [rng.randrange(1, N) for _ in range(300)]
+    assert all(1 <= x < N for x in v)
+    return tuple(v)
+
+
+HIT_WINDOWS = (0, 1, 7, 8, 14, 15)
+CombCase = collections.namedtuple('CombCase', 'name i kind shape role u1 u2 d case')
+
+
+@functools.lru_cache(maxsize=None)
+def comb_cases():
+    """Comb collisions: per hit window i, kind, shape of u1 and value of w_i one 'hit' and its siblings:
+    'miss_sum' (the partial sum off by one), 'miss_window' (the same key, u1 + 2^(16 i)) and 'scaled'
+    ((2r, 2s, 2e): the same u1, u2 and path, so the same hit, but r no longer x(R): invalid).  Shapes:
+    'only' (window i alone), 'below' (windows below i too; none for i = 0), 'above' (windows above i too;
+    none for i = 15)."""
+    rng = random.Random(1601)
+    out = []
+    for i in HIT_WINDOWS:
+        shapes = ['only'] + (['below'] if i > 0 else []) + (['above'] if i < COMB_WINDOWS - 1 else [])
+        for kind in ('double', 'cancel'):
+            for shape in shapes:
+                for wi in (1, 0xFFFF, 0x8000, rng.randrange(2, 0xFFFF)):
+                    windows = [0] * COMB_WINDOWS
+                    windows[i] = wi
+                    others = list(range(i)) if shape == 'below' else list(range(i + 1, COMB_WINDOWS))
+                    if shape != 'only':
+                        for j in set(rng.sample(others, rng.randint(1, min(3, len(others)))) + [others[-1]]):
+                            windows[j] = rng.randrange(1, 0xFFFF)
+                    u2 = rng.randrange(1, N)
+                    name = 'w%d_%s_%s_%04x' % (i, kind, shape, wi)
+                    u1, d, case = hit_case(windows, i, kind, u2)
+                    out.append(CombCase(name, i, kind, shape, 'hit', u1, u2, d, case))
+                    # off by +1; by -1 where +1 would ask for d = 0 (window 0 cancelling the entry 1 G: -1 + 1)
+                    off = -1 if (i, kind, wi) == (0, 'cancel', 1) else 1
+                    _, d1, c1 = hit_case(windows, i, kind, u2, off=off)
+                    out.append(CombCase(name + '_miss_sum', i, kind, shape, 'miss_sum', u1, u2, d1, c1))
+                    up = (u1 + (1 << (COMB_BITS * i))) % N
+                    out.append(CombCase(name + '_miss_window', i, kind, shape, 'miss_window', up, u2, d, from_u(up, u2, d)))
+                    scaled = Case(case.Q, 2 * case.r % N, 2 * case.s % N, 2 * case.e % N, False)
+                    out.append(CombCase(name + '_scaled', i, kind, shape, 'scaled', u1, u2, d, scaled))
+    return tuple(out)
+
+
+ScalarCase = collections.namedtuple('ScalarCase', 'name family Q r s digest valid')
+
+
+@functools.lru_cache(maxsize=None)
+def scalar_cases():
+    """Valid signatures with u2, s or u1 forced to each value of V (u1 also to 0), and with an unreduced
+    digest e + n; after every fifth one three mutants (one bit flipped in r, in s, in the digest) with the
+    verdict of ``verify_digest``."""
+    rng = random.Random(1602)
+    V = _scalar_set()
+    base = []
+    for j, v in enumerate(V):
+        c = from_u(rng.randrange(N), v, rng.randrange(1, N))
+        base.append(ScalarCase('u2_%d' % j, 'u2', c.Q, c.r, c.s, c.e, c.valid))
+    for j, v in enumerate(V):
+        c = from_s(rng.randrange(1, N), v, rng.getrandbits(256))
+        base.append(ScalarCase('s_%d' % j, 's', c.Q, c.r, c.s, c.e, c.valid))
+    for j, v in enumerate((0,) + V):
+        c = from_u(v, rng.randrange(1, N), rng.randrange(1, N))
+        base.append(ScalarCase('u1_%d' % j, 'u1', c.Q, c.r, c.s, c.e, c.valid))
+    top = 2 ** 256 - N  # e + n stays below 2^256 for e < top
+    small = [0, 1, top - 1, top - 2, 2 ** 128, 2 ** 64 - 1] + [rng.randrange(top) for _ in range(58)]
+    for j, e in enumerate(small):
+        c = from_s(rng.randrange(1, N), rng.randrange(1, N), e)
+        assert N <= e + N < 2 ** 256
+        base.append(ScalarCase('e_plus_n_%d' % j, 'e_plus_n', c.Q, c.r, c.s, e + N, c.valid))
+    out = []
+    for j, c in enumerate(base):
+        assert c.valid
+        out.append(c)
+        if j % 5:
+            continue
+        for field in ('r', 's', 'digest'):
+            while True:
+                val = getattr(c, field) ^ (1 << rng.randrange(256))
+                if field == 'digest' or 1 <= val < N:
+                    break
+            m = c._replace(name='%s_flip_%s' % (c.name, field), family=c.family + '_mutant', **{field: val})
+            out.append(m._replace(valid=verify_digest(m.Q, m.r, m.s, m.digest)))
+    return tuple(out)
+
+
+HASH_LENGTHS = tuple(range(261)) + (4095, 4096, 4097)
+HashCase = collections.namedtuple('HashCase', 'name msg sig key code')
+
+
+@functools.lru_cache(maxsize=None)
+def hash_cases():
+    """One message per length of HASH_LENGTHS, signed under SHA-1 (even lengths) or SHA-256 (odd ones) by
+    one of four keys, and the same signature over the message with its last byte changed (a byte appended
+    to the empty one); ``code`` is ``verify``'s."""
+    rng = random.Random(1603)
+    keys = [rng.randrange(1, N) for _ in range(4)]
+    pubs = [xy_key(mult_g(d)) for d in keys]
+    out = []
+    for j, ln in enumerate(HASH_LENGTHS):
+        msg = bytes(rng.getrandbits(8) for _ in range(ln))
+        alg = hashlib.sha256 if ln % 2 else hashlib.sha1
+        sig = der_encode(*sign(keys[j % 4], rng.randrange(1, N), int.from_bytes(alg(msg).digest(), 'big')))
+        out.append(HashCase('len%d' % ln, msg, sig, pubs[j % 4], verify(msg, sig, pubs[j % 4])))
+        bad = msg[:-1] + bytes([msg[-1] ^ 1]) if msg else b'\x00'
+        out.append(HashCase('len%d_changed' % ln, bad, sig, pubs[j % 4], verify(bad, sig, pubs[j % 4])))
+    return tuple(out)

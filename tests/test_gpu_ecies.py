@@ -96,6 +96,32 @@ def test_ecdh_is_strict(gpulib, pairs):
     assert out.raw[32:64] == b'\x00' * 32
 
 
+def test_ecdh_on_many_points(gpulib):
+    """``var_table`` and the ladder on 256 points m G (m structured and random), 4 structured keys each,
+    against the integer oracle (``oracle/ecdsa_oracle.py``): x(k m G), one fixed-base multiplication per
+    pair; every eighth point also negated (the same x) and with y + 1 (off the curve: refused)."""
+    from oracle import ecdsa_oracle as eo
+    rng = random.Random(23)
+    V = eo.scalar_set()
+    ms = V[:7] + V[7::6][:121] + [rng.randrange(1, N) for _ in range(128)]
+    assert len(ms) == 256 and {1, N - 1} <= set(ms)
+    keys, points, want = [], [], []
+    for j, m in enumerate(ms):
+        x, y = eo.mult_g(m)
+        ks = rng.sample(V, 4)
+        shared = [b32(eo.mult_g(k * m % N)[0]) for k in ks]
+        for pt, sx in (((x, y), shared), ((x, P - y), shared), ((x, (y + 1) % P), [None] * 4)):
+            if pt[1] != y and j % 8:
+                continue
+            assert eo.on_curve(pt) == (sx[0] is not None)
+            keys += [b32(k) for k in ks]
+            points += [(b32(pt[0]), b32(pt[1]))] * 4
+            want += sx
+    assert len(want) == 4 * (256 + 32 + 32) and want.count(None) == 128
+    got = ecies.ecdh(keys, points)
+    assert got == want, [i for i, (g, w) in enumerate(zip(got, want)) if g != w][:10]
+
+
 # ------------------------------------------------------------------ match
 def test_match_msg_kats_against_the_three_keys(gpulib, kats):
     keys = [bytes.fromhex(k) for k in kats['recipient_keys']]

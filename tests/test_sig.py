@@ -11,6 +11,7 @@ import subprocess
 
 import pytest
 
+from oracle.ecdsa_oracle import der_decode
 from pybitmessage_amd import _lib, signatures
 from tests.conftest import ROOT
 
@@ -72,22 +73,7 @@ def test_verdict_codes_match_the_header():
 
 
 # ------------------------------------------------------------------ DER
-def py_der(sig):
-    """Python's own strict decode: (r, s) of a canonical DER SEQUENCE { INTEGER, INTEGER }, else None."""
-    def integer(b):
-        if len(b) < 2 or b[0] != 2 or b[1] >= 0x80 or b[1] == 0 or len(b) < 2 + b[1]:
-            return None
-        v = b[2:2 + b[1]]
-        if v[0] & 0x80 or (len(v) > 1 and v[0] == 0 and not v[1] & 0x80):
-            return None
-        return int.from_bytes(v, 'big'), b[2 + b[1]:]
-    if len(sig) < 2 or sig[0] != 0x30 or sig[1] >= 0x80 or sig[1] != len(sig) - 2:
-        return None
-    r = integer(sig[2:])
-    s = integer(r[1]) if r else None
-    if not s or s[1]:
-        return None
-    return r[0], s[0]
+py_der = der_decode  # Python's own strict decode: (r, s) of a canonical DER SEQUENCE { INTEGER, INTEGER }, else None
 
 
 def test_parse_against_every_fixture_signature(kats):

@@ -324,7 +324,9 @@ BMPOW_API int bmpow_fe_probe(int op, size_t n, const uint32_t *a, const uint32_t
 /* Deterministic addresses (createDeterministicAddresses / getDeterministicAddress / chans):
  * privSigning = SHA512(passphrase || varint(2k))[:32], privEncryption = SHA512(passphrase ||
  * varint(2k+1))[:32], k in [start, start + max_tries).  Returns BMPOW_FOUND (out filled) with
- * the first k, BMPOW_NOT_FOUND, or < 0.  The reference continues the next address at k + 1. */
+ * the first k, BMPOW_NOT_FOUND, or < 0.  The reference continues the next address at k + 1.
+ * The tries end at k = 2^63 - 1, whose nonces 2^64 - 2 and 2^64 - 1 are the last a varint holds: a
+ * range that reaches past it is searched up to there, and start >= 2^63 is BMPOW_E_ARG. */
 BMPOW_API int bmpow_address_search(const uint8_t *passphrase, size_t len, uint64_t start, uint64_t max_tries,
                                    int null_bytes, bmpow_address *out);
 

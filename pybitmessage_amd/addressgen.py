@@ -26,6 +26,9 @@ from . import _lib
 ALPHABET = '123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz'
 #: tries per bounded device call (the caller's shutdown-poll interval)
 CALL_TRIES = 1 << 24
+#: deterministic tries end below this k: try 2^63 - 1 uses the nonces 2^64 - 2 and 2^64 - 1, the last
+#: ones ``encodeVarint`` takes (the reference's loop raises there)
+DETERMINISTIC_TRIES = 1 << 63
 
 
 def encodeVarint(integer):
@@ -118,15 +121,15 @@ def _interrupted():
 
 def search_deterministic(passphrase, null_bytes=1, start=0, max_tries=None):
     """First try k >= start of the deterministic loop whose ripe meets the prefix, as a
-    :class:`Found`; None when ``max_tries`` run out.  Bounded device calls; raises
-    ``StopIteration('Interrupted')`` on ``state.shutdown`` between them."""
+    :class:`Found`; None when ``max_tries`` run out or the tries do (k = 2^63 - 1 is the last one).
+    Bounded device calls; raises ``StopIteration('Interrupted')`` on ``state.shutdown`` between them."""
     if isinstance(passphrase, str):
         passphrase = passphrase.encode('utf-8')
     lib = _lib.get()
     out = _lib.BmpowAddress()
     k = start
     left = max_tries
-    while left is None or left > 0:
+    while (left is None or left > 0) and (k < DETERMINISTIC_TRIES or k == start):  # a start above: E_ARG
         if _interrupted():
             raise StopIteration('Interrupted')
         n = CALL_TRIES if left is None else min(CALL_TRIES, left)

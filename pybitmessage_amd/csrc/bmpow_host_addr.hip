@@ -159,7 +159,10 @@ int addr_search_locked(uint32_t mode, const uint8_t* seed, size_t len, const uin
     HIPTRY(hipMemcpy(&ok, as[0].d_ok.get(), sizeof ok, hipMemcpyDeviceToHost));
     if (!ok) return set_err(BMPOW_E_ARG, "signing private key is zero");
   }
-  const uint64_t end = (kU64Max - start < max_tries) ? kU64Max : start + max_tries;
+  uint64_t end = (kU64Max - start < max_tries) ? kU64Max : start + max_tries;
+  // mode 0: k = 2^63 - 1 is the last try there is (its nonce 2k + 1 = 2^64 - 1 is the last a varint
+  // holds); a lane above it would derive its keys from the wrapped nonce
+  if (mode == 0) end = std::min<uint64_t>(end, 1ULL << 63);
   const int comb = addr_pick_comb(null_bytes);
   if (comb < 0) return comb;
   g_addr_last_comb = kCombBits[comb];

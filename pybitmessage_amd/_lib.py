@@ -215,6 +215,33 @@ SIG_SIGNATURES = [
     ('bmpow_sig_reset_stats', None, []),
 ]
 
+
+
+class BmpowSendStats(ctypes.Structure):
+    """``bmpow_send_stats`` (include/bmpow_send.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('sets', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('hash_ms', ctypes.c_double), ('comb_ms', ctypes.c_double),
+                ('scalar_ms', ctypes.c_double), ('ladder_ms', ctypes.c_double), ('seal_ms', ctypes.c_double),
+                ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_send.h declares
+SEND_SIGNATURES = [
+    ('bmpow_ec_pubkeys', ctypes.c_int, [ctypes.c_size_t, ctypes.c_char_p, _pu8, _pu8]),
+    ('bmpow_ecdsa_sign_digest', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _pu8, _pu8]),
+    ('bmpow_sig_der', ctypes.c_int, [ctypes.c_char_p, _pu8, ctypes.POINTER(ctypes.c_size_t)]),
+    ('bmpow_sig_sign', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, _pu8, _pu8]),
+    ('bmpow_ecies_seal', ctypes.c_int64,
+     [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _pu8, ctypes.c_size_t]),
+    ('bmpow_ecies_encrypt', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, _p64,
+      _p64]),
+    ('bmpow_send_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowSendStats)]),
+    ('bmpow_send_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -232,7 +259,7 @@ def load(path=None):
         raise BmpowUnavailable(E_NODEV, 'libbmpow_hip.so not built at %s (run __graft_entry__.build() '
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
-    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES:
+    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES:
         try:
             fn = getattr(lib, name)
         except AttributeError:

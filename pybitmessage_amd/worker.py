@@ -351,6 +351,69 @@ def msg_object(encrypted, to_address_version, stream, ttl, ntpb=None, extra=None
 
 
 # ------------------------------------------------------------------------------------------
+# the whole send path of a msg: ack PoW -> sign -> encrypt -> msg PoW, every step a batch
+# ------------------------------------------------------------------------------------------
+def msg_plaintext(from_address_version, from_stream, bitfield, pub_signing, pub_encryption, to_ripe, encoding,
+                  message, full_ack_payload=b'', ntpb=None, extra=None):
+    """The unsigned body of a msg as ``sendMsg`` assembles it (``:1136-1223``): sender address version
+    and stream, the 4-byte bitfield, the two public keys without their 0x04 prefix, for address version
+    >= 3 the sender's own difficulty (``ntpb``, ``extra``; the network defaults when None), ``toRipe``,
+    the encoding, the length-prefixed encoded message and the length-prefixed ``fullAckPayload``."""
+    payload = _varint(from_address_version) + _varint(from_stream) + bytes(bitfield)
+    payload += bytes(pub_signing)[-64:] + bytes(pub_encryption)[-64:]
+    if from_address_version >= 3:
+        n, e = _defaults(ntpb, extra)
+        payload += _varint(n) + _varint(e)
+    message, full_ack_payload = bytes(message), bytes(full_ack_payload)
+    payload += bytes(to_ripe) + _varint(encoding) + _varint(len(message)) + message
+    return payload + _varint(len(full_ack_payload)) + full_ack_payload
+
+
+def send_msgs_signed(jobs, build_plain, rng=random, now=None, step_trials=0):
+    """Batched ``sendMsg`` (``:717-1373``) with the signing and the encryption in the library: ack PoW,
+    sign, encrypt, msg PoW, each one batch.
+
+    ``jobs``: ``[(ackdata_or_None, ttl, ctx), ...]`` as for :func:`send_msgs`.  Phase 1 PoWs every ack.
+    Then ``build_plain(ctx, fullAckPayload) -> (plaintext, signing_privkey, recipient_pubkey,
+    to_address_version, stream, ttl, ntpb, extra)`` gives each msg's unsigned body
+    (:func:`msg_plaintext`), the sender's private signing key (32 raw bytes), the recipient's public
+    encryption key (64 or 65 raw bytes), and the recipient's address version, stream and difficulty
+    (``ntpb`` / ``extra`` None: the network defaults; :func:`msg_difficulty` raises a lower demand to
+    them, ``:1008-1027``).  ``embeddedTime`` is fixed once per msg; the
+    signature covers ``pack('>Q', embeddedTime) + '\\x00\\x00\\x00\\x02' + varint(1) + varint(stream) +
+    plaintext`` (``:1224``) under SHA-256 and is appended with its length (``:1227-1228``); the whole is
+    encrypted to the recipient (``:1232``) and wrapped into the msg object with the same
+    ``embeddedTime`` (``:1252-1255``); phase 2 PoWs every msg at the recipient's difficulty.  Returns the
+    finished msg objects in job order; None for a msg whose recipient key is refused (the reference's
+    "encrypt didn't work") and for an object above 256 KiB."""
+    from . import sender
+    jobs = list(jobs)
+    want_ack = [k for k, (ackdata, _, _) in enumerate(jobs) if ackdata is not None]
+    packets = full_ack_messages([(jobs[k][0], jobs[k][1]) for k in want_ack], rng, now, step_trials)
+    ack_of = dict(zip(want_ack, packets))
+    built = [build_plain(ctx, ack_of.get(k, b'')) for k, (_, _, ctx) in enumerate(jobs)]
+    heads = [pack('>Q', _embedded(ttl, now)) + b'\x00\x00\x00\x02' + _varint(1) + _varint(stream)
+             for _, _, _, _, stream, ttl, _, _ in built]
+    plains = [bytes(b[0]) for b in built]
+    sigs = sender.sign_batch([h + p for h, p in zip(heads, plains)], [b[1] for b in built], 'sha256')
+    live = [k for k, s in enumerate(sigs) if s is not None]
+    blobs = sender.encrypt_batch([plains[k] + _varint(len(sigs[k])) + sigs[k] for k in live], [built[k][2] for k in live])
+    msgs = []
+    for k, blob in zip(live, blobs):
+        if blob is None:
+            logger.warning("encrypt didn't work: the recipient's encryption key of msg %d is no good", k)
+            continue
+        _, _, _, version, _, ttl, ntpb, extra = built[k]
+        n, e = msg_difficulty(version, ntpb, extra)
+        msgs.append(PowObject(heads[k] + blob, ttl, n, e, tag=k))
+    out = [None] * len(jobs)
+    for m, o in zip(msgs, pow_objects(msgs, step_trials)):
+        if len(o) <= MAX_OBJECT_SIZE:
+            out[m.tag] = o
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # continuous batching across producer threads
 # ------------------------------------------------------------------------------------------
 class _Group(object):

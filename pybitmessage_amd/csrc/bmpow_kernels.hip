@@ -87,6 +87,10 @@ __device__ __forceinline__ bm_swept sweep(const bm_item& it, uint32_t qi, const 
   }
   __syncthreads();
   bm_swept r = {0, 0, 0};
+  // the search kernels' trial (sha512_dev.h kSearch); the single-object kernel keeps the plain one
+  // unless BM_STEER_ONE
+  constexpr bool kSearch = !kOne || BM_STEER_ONE;
+  constexpr bool kSteered = kSearch && BM_STEER != 0;
 #if BM_LAG_PRIO
   unsigned long long kprev = s_k[0];
 #endif
@@ -98,6 +102,9 @@ __device__ __forceinline__ bm_swept sweep(const bm_item& it, uint32_t qi, const 
 #ifdef BM_PRIO_MOD
   if (blockIdx.x % BM_PRIO_MOD == 0) __builtin_amdgcn_s_setprio(2);  // A/B knob: a share of the waves issue first
 #endif
+  // steered 3-input ops (sha512_dev.h): the wave's priority outside its units, from here to the end of
+  // the nonce loop.  Every path into the loop is wave-uniform (s_k is shared, bestp one address).
+  if constexpr (kSteered) __builtin_amdgcn_s_setprio(BM_STEER_BASE);
   uint64_t ihw[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -134,14 +141,14 @@ __device__ __forceinline__ bm_swept sweep(const bm_item& it, uint32_t qi, const 
       uint64_t tv;
       if constexpr (kOne && BM_CUT) {
         bool c = false;
-        tv = trial_of_cut(
+        tv = trial_of_cut<kSearch>(
             ihw, nonce, [&] { return __hip_atomic_load(bestp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < first; }, c);
         if (c) {
           r.cut += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
           live = false;
         }
       } else {
-        tv = trial_of(ihw, nonce);
+        tv = trial_of<kSearch>(ihw, nonce);
       }
 #endif
       // Wavefront min-reduction of the hits: a wave's 64 nonces are consecutive, so its smallest hit
@@ -218,7 +225,18 @@ __device__ __forceinline__ bm_swept sweep(const bm_item& it, uint32_t qi, const 
     if (nu >= nunit || seen < it.start + nu * (BM_GRAB * BM_BLOCK)) break;
     unit = nu;
   }
+  if constexpr (kSteered) __builtin_amdgcn_s_setprio(0);
   return r;
+}
+
+// The relay workgroup of a kX launch beside steered columns: it runs at the columns' BASE.  Its poll loop
+// is a few VALU instructions between sleeps; left at 0 under columns that stand at BASE (or, in the
+// control sense, never below it) it would be the arbiter's last choice on a SIMD whose VALU is issued in
+// 99.8 % of its cycles, and a late fold of another shard's hit only costs trials, but a relay that cannot
+// see the columns finish holds the launch.  At BASE it is what it was: the oldest wave among equals.
+template <bool kSteeredColumns>
+__device__ __forceinline__ void bm_steer_relay_prio() {
+  if constexpr (kSteeredColumns && BM_STEER != 0) __builtin_amdgcn_s_setprio(BM_STEER_BASE);
 }
 
 // One workgroup of a batch launch: the item holding workgroup b (the largest item index with
@@ -263,6 +281,7 @@ __global__ __launch_bounds__(BM_BLOCK, BM_SEARCH_WAVES) void bm_search_kernel(co
                                                              uint32_t xrow, uint32_t xrows) {
   if constexpr (kX) {
     if (blockIdx.x == 0) {
+      bm_steer_relay_prio<true>();
       bm_relay(items, nitems, best, xb, xrow, trials_done + 1, (gridDim.x - 1) * (BM_BLOCK / 64));
       return;
     }
@@ -348,6 +367,7 @@ __global__ __launch_bounds__(BM_BLOCK, BM_SEARCH_WAVES) void bm_search1_kernel(c
   if constexpr (kX) {
     if (blockIdx.x == 0) {
       if (threadIdx.x != 0) return;
+      bm_steer_relay_prio<BM_STEER_ONE != 0>();
       unsigned long long* const slot = a.xb + (size_t)a.xrow * BM_XSLOTS + a.xslot;
       uint64_t seen = ~0ULL;
       // bounded (2^26 polls, over a minute) so a lost column cannot keep the relay forever; the last

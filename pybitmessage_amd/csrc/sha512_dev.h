@@ -111,10 +111,68 @@ BM_DEV uint64_t opaque(uint64_t x) {
   return x;
 }
 
+// ---- in-stream wave priority around the 3-input ops ("Steered 3-input ops") ----
+// v_bitop3_b32 is the one instruction of the trial that can share a quad-cycle with another wave's.
+// A steered unit is `s_setprio LOW; its v_bitop3_b32; s_setprio BASE`: a wave standing at a bitop3
+// yields to waves with half-rate work, so that the waves left at the head of the arbiter are all
+// pairable.  Measured on one MI355X (profiles/steer/): the paired share of the VALU instructions rises
+// from 6.0 % to 27.0 %, 1.0625 -> 1.3665 instructions per SIMD quad-cycle at the same 6,182.7 VALU per
+// trial, the default bench 6.687 -> 8.454 GH/s; the opposite sense (LOW > BASE) is 4 % slower than no
+// steering.  s_setprio is not a VALU instruction and costs no VALU issue slot.
+// Only the batch search kernel's trial (kSearch below) is steered; every other user of this header
+// keeps the plain stream, which stays an independent check of the steered one.
+//   BM_STEER       0: off.  The size of a unit in v_bitop3_b32: 2 (one 64-bit function), 4 (Sigma1 with
+//                  Ch, Sigma0 with Maj: the default) or 8 (a round's eight, the BM_GROUP_BITOP3 block).
+//   BM_STEER_BASE / BM_STEER_LOW   the priority outside / inside a unit.  LOW < BASE is the hypothesis,
+//                  LOW > BASE its control.  The sweep sets BASE before its nonce loop and 0 after it.
+//   BM_STEER_SCHED 1: the message schedule's sigma0 / sigma1 are steered too (as units of 2); without
+//                  them the gain is a third smaller (C3 7.96 against 8.54 GH/s).
+//   BM_STEER_ONE   1: the single-object kernel (bm_search1_kernel) is steered too.  Off: its calls get
+//                  shorter (C1 1.350 against 1.687 ms) but hash more nonces past the answer (median
+//                  1.06 % against 0.34 %, worst call 16 % against 2.6 %): younger waves are starved
+//                  while they hold the block with the answer.
+#ifndef BM_STEER
+#define BM_STEER 4
+#endif
+#ifndef BM_STEER_ONE
+#define BM_STEER_ONE 0
+#endif
+#ifndef BM_STEER_BASE
+#define BM_STEER_BASE 1
+#endif
+#ifndef BM_STEER_LOW
+#define BM_STEER_LOW 0
+#endif
+#ifndef BM_STEER_SCHED
+#define BM_STEER_SCHED 1
+#endif
+// BM_HOIST_S0 (A/B knob, off): in the kSearch trial's block 1, sigma0 of the per-object W17, W19, W21
+// (T = 32, 34, 36) takes the hoistable form too.  It should save 21 VALU per trial; the loop loses 9 (the
+// rotates stay inside), and the unsteered kernel ran 4.7 % slower with it (C3 6.415 against 6.732 GH/s).
+#ifndef BM_HOIST_S0
+#define BM_HOIST_S0 0
+#endif
+static_assert(BM_STEER == 0 || BM_STEER == 2 || BM_STEER == 4 || BM_STEER == 8, "BM_STEER: 0, 2, 4 or 8");
+static_assert(BM_STEER_BASE >= 0 && BM_STEER_BASE <= 3 && BM_STEER_LOW >= 0 && BM_STEER_LOW <= 3, "s_setprio: 0..3");
+
 // kHoist: a per-object (wave-uniform) value LICM hoists out of the nonce loop -- no opaque barrier,
 // which would pin a register copy of it inside the loop.
-template <uint8_t LUT, bool kHoist = false>
+// kSteer: one steered unit of two (never with kHoist: LICM does not lift asm).  Not volatile: a unit
+// whose result is unused goes with it.  The low half's output is early-clobber, since the second
+// instruction still reads its inputs after the first has written.
+template <uint8_t LUT, bool kHoist = false, bool kSteer = false>
 BM_DEV uint64_t bitop3_64(uint64_t a, uint64_t b, uint64_t c) {
+  if constexpr (kSteer && !kHoist) {
+    uint32_t l, h;
+    asm("s_setprio %8\n\t"
+        "v_bitop3_b32 %0, %2, %3, %4 bitop3:%10\n\t"
+        "v_bitop3_b32 %1, %5, %6, %7 bitop3:%10\n\t"
+        "s_setprio %9"
+        : "=&v"(l), "=v"(h)
+        : "v"(lo32(a)), "v"(lo32(b)), "v"(lo32(c)), "v"(hi32(a)), "v"(hi32(b)), "v"(hi32(c)), "n"(BM_STEER_LOW),
+          "n"(BM_STEER_BASE), "n"((int)LUT));
+    return opaque(mk64(l, h));
+  }
   const uint64_t r = mk64(bitop3<LUT>(lo32(a), lo32(b), lo32(c)), bitop3<LUT>(hi32(a), hi32(b), hi32(c)));
   if constexpr (kHoist) return r;
   return opaque(r);
@@ -137,24 +195,28 @@ BM_DEV uint64_t add64(uint64_t a, uint64_t b) {
   return a + b;
 }
 
-template <bool kHoist = false>
-BM_DEV uint64_t xor3(uint64_t a, uint64_t b, uint64_t c) { return bitop3_64<0x96, kHoist>(a, b, c); }
+template <bool kHoist = false, bool kSteer = false>
+BM_DEV uint64_t xor3(uint64_t a, uint64_t b, uint64_t c) { return bitop3_64<0x96, kHoist, kSteer>(a, b, c); }
 
 // FIPS 180-4 4.1.3 functions.
-BM_DEV uint64_t Sig0(uint64_t a) { return xor3(rotr<28>(a), rotr<34>(a), rotr<39>(a)); }
-BM_DEV uint64_t Sig1(uint64_t e) { return xor3(rotr<14>(e), rotr<18>(e), rotr<41>(e)); }
-template <bool kSplit = false>
+template <bool kSteer = false>
+BM_DEV uint64_t Sig0(uint64_t a) { return xor3<false, kSteer>(rotr<28>(a), rotr<34>(a), rotr<39>(a)); }
+template <bool kSteer = false>
+BM_DEV uint64_t Sig1(uint64_t e) { return xor3<false, kSteer>(rotr<14>(e), rotr<18>(e), rotr<41>(e)); }
+template <bool kSplit = false, bool kSteer = false>
 BM_DEV uint64_t sig0(uint64_t w) {
   if (__builtin_constant_p(w)) return (w >> 1 | w << 63) ^ (w >> 8 | w << 56) ^ (w >> 7);
-  return xor3<kSplit>(rotr<1>(w), rotr<8>(w), shr<7, kSplit>(w));
+  return xor3<kSplit, kSteer>(rotr<1>(w), rotr<8>(w), shr<7, kSplit>(w));
 }
-template <bool kSplit = false>
+template <bool kSplit = false, bool kSteer = false>
 BM_DEV uint64_t sig1(uint64_t w) {
   if (__builtin_constant_p(w)) return (w >> 19 | w << 45) ^ (w >> 61 | w << 3) ^ (w >> 6);
-  return xor3<kSplit>(rotr<19>(w), rotr<61>(w), shr<6, kSplit>(w));
+  return xor3<kSplit, kSteer>(rotr<19>(w), rotr<61>(w), shr<6, kSplit>(w));
 }
-BM_DEV uint64_t Ch(uint64_t e, uint64_t f, uint64_t g) { return bitop3_64<0xCA>(e, f, g); }
-BM_DEV uint64_t Maj(uint64_t a, uint64_t b, uint64_t c) { return bitop3_64<0xE8>(a, b, c); }
+template <bool kSteer = false>
+BM_DEV uint64_t Ch(uint64_t e, uint64_t f, uint64_t g) { return bitop3_64<0xCA, false, kSteer>(e, f, g); }
+template <bool kSteer = false>
+BM_DEV uint64_t Maj(uint64_t a, uint64_t b, uint64_t c) { return bitop3_64<0xE8, false, kSteer>(a, b, c); }
 
 // constexpr twins (host + device) for compile-time folding of IV-only expressions.
 constexpr uint64_t crotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
@@ -184,55 +246,106 @@ constexpr uint64_t PAD = 0x8000000000000000ULL;
 // kVar0: block 0 of a trial over an initialHash of any other length (trial_var): W1..W15 are all
 // per-object (uniform, not compile-time), so the sigma0 of W1..W15 (T = 16..30) and the sigma1 of
 // W14, W15, W17, W19, W21 (T = 16, 17, 19, 21, 23) are hoistable.
-template <int T, bool kTrial1 = false, bool kVar0 = false>
+// kSearch: the search kernels' instantiation (trial_of<true>, trial_of_cut<true>): the 3-input ops of
+// rounds 3.. are steered units (BM_STEER; rounds 1 and 2 mix in IV constants, which an asm operand would
+// pin in VGPRs), and BM_HOIST_S0 applies.
+template <int T, bool kTrial1 = false, bool kVar0 = false, bool kSearch = false>
 BM_DEV void round_step(uint64_t (&s)[8], uint64_t (&w)[16]) {
   constexpr int A = (8 - (T & 7)) & 7;
   constexpr int B = (A + 1) & 7, C = (A + 2) & 7, D = (A + 3) & 7;
   constexpr int E = (A + 4) & 7, F = (A + 5) & 7, G = (A + 6) & 7, H = (A + 7) & 7;
+  constexpr int kUnit = (kSearch && T >= 3) ? BM_STEER : 0;  // v_bitop3_b32 per steered unit, 0: plain
   if constexpr (T >= 16) {
-    constexpr bool kU0 = (kTrial1 && T <= 23) || (kVar0 && T <= 30);
+    constexpr bool kU0 = (kTrial1 && T <= 23) || (kVar0 && T <= 30) ||
+                         (kTrial1 && kSearch && BM_HOIST_S0 && (T == 32 || T == 34 || T == 36));
     constexpr bool kU1 = (kTrial1 && (T == 19 || T == 21 || T == 23)) ||
                          (kVar0 && (T == 16 || T == 17 || T == 19 || T == 21 || T == 23));
+    constexpr bool kSw = kUnit != 0 && BM_STEER_SCHED;
     // grouped so the terms that do not depend on the nonce (per-object or compile-time)
     // are summed first and hoisted out of the nonce loop by LICM
-    w[T & 15] = (w[(T - 7) & 15] + sig0<kU0>(w[(T - 15) & 15]) + w[(T - 16) & 15]) + sig1<kU1>(w[(T - 2) & 15]);
+    w[T & 15] = (w[(T - 7) & 15] + sig0<kU0, kSw>(w[(T - 15) & 15]) + w[(T - 16) & 15]) + sig1<kU1, kSw>(w[(T - 2) & 15]);
   }
 #ifdef BM_GROUP_BITOP3
-  // A/B variant: the round's eight 3-input ops (Sigma1 / Sigma0 XOR3, Ch, Maj on both halves) issue
-  // back to back, so waves sharing a SIMD meet at them together more often (they co-issue only
-  // with each other); rotates and adds stay the compiler's.
-  const uint64_t e = s[E], a = s[A];
-  const uint64_t r14 = rotr<14>(e), r18 = rotr<18>(e), r41 = rotr<41>(e);
-  const uint64_t r28 = rotr<28>(a), r34 = rotr<34>(a), r39 = rotr<39>(a);
-  uint32_t s1l, s1h, s0l, s0h, chl, chh, mjl, mjh;
-  asm("v_bitop3_b32 %0, %8, %9, %10 bitop3:0x96\n\t"
-      "v_bitop3_b32 %1, %11, %12, %13 bitop3:0x96\n\t"
-      "v_bitop3_b32 %2, %14, %15, %16 bitop3:0x96\n\t"
-      "v_bitop3_b32 %3, %17, %18, %19 bitop3:0x96\n\t"
-      "v_bitop3_b32 %4, %20, %21, %22 bitop3:0xca\n\t"
-      "v_bitop3_b32 %5, %23, %24, %25 bitop3:0xca\n\t"
-      "v_bitop3_b32 %6, %26, %27, %28 bitop3:0xe8\n\t"
-      "v_bitop3_b32 %7, %29, %30, %31 bitop3:0xe8"
-      : "=&v"(s1l), "=&v"(s1h), "=&v"(s0l), "=&v"(s0h), "=&v"(chl), "=&v"(chh), "=&v"(mjl), "=&v"(mjh)
-      : "v"(lo32(r14)), "v"(lo32(r18)), "v"(lo32(r41)), "v"(hi32(r14)), "v"(hi32(r18)), "v"(hi32(r41)),
-        "v"(lo32(r28)), "v"(lo32(r34)), "v"(lo32(r39)), "v"(hi32(r28)), "v"(hi32(r34)), "v"(hi32(r39)),
-        "v"(lo32(e)), "v"(lo32(s[F])), "v"(lo32(s[G])), "v"(hi32(e)), "v"(hi32(s[F])), "v"(hi32(s[G])),
-        "v"(lo32(a)), "v"(lo32(s[B])), "v"(lo32(s[C])), "v"(hi32(a)), "v"(hi32(s[B])), "v"(hi32(s[C])));
-  const uint64_t t1 = add64(add64(add64(s[H], opaque(mk64(s1l, s1h))), opaque(mk64(chl, chh))), K(T) + w[T & 15]);
-  s[D] = add64(s[D], t1);
-  s[H] = add64(add64(t1, opaque(mk64(s0l, s0h))), opaque(mk64(mjl, mjh)));
+  constexpr bool kGroup = true;
 #else
-  const uint64_t t1 = add64(add64(add64(s[H], Sig1(s[E])), Ch(s[E], s[F], s[G])), K(T) + w[T & 15]);
-  s[D] = add64(s[D], t1);
-  s[H] = add64(add64(t1, Sig0(s[A])), Maj(s[A], s[B], s[C]));
+  constexpr bool kGroup = kUnit == 8;
 #endif
+  if constexpr (kGroup) {
+    // A/B variant: the round's eight 3-input ops (Sigma1 / Sigma0 XOR3, Ch, Maj on both halves) issue
+    // back to back, so waves sharing a SIMD meet at them together more often (they co-issue only
+    // with each other); rotates and adds stay the compiler's.  As a steered unit of 8 the block stands
+    // inside one priority pair.
+    const uint64_t e = s[E], a = s[A];
+    const uint64_t r14 = rotr<14>(e), r18 = rotr<18>(e), r41 = rotr<41>(e);
+    const uint64_t r28 = rotr<28>(a), r34 = rotr<34>(a), r39 = rotr<39>(a);
+    uint32_t s1l, s1h, s0l, s0h, chl, chh, mjl, mjh;
+#define BM_GROUP8_                                   \
+  "v_bitop3_b32 %0, %8, %9, %10 bitop3:0x96\n\t"    \
+  "v_bitop3_b32 %1, %11, %12, %13 bitop3:0x96\n\t"  \
+  "v_bitop3_b32 %2, %14, %15, %16 bitop3:0x96\n\t"  \
+  "v_bitop3_b32 %3, %17, %18, %19 bitop3:0x96\n\t"  \
+  "v_bitop3_b32 %4, %20, %21, %22 bitop3:0xca\n\t"  \
+  "v_bitop3_b32 %5, %23, %24, %25 bitop3:0xca\n\t"  \
+  "v_bitop3_b32 %6, %26, %27, %28 bitop3:0xe8\n\t"  \
+  "v_bitop3_b32 %7, %29, %30, %31 bitop3:0xe8"
+#define BM_GROUP8_OPS_                                                                                        \
+  : "=&v"(s1l), "=&v"(s1h), "=&v"(s0l), "=&v"(s0h), "=&v"(chl), "=&v"(chh), "=&v"(mjl), "=&v"(mjh)            \
+  : "v"(lo32(r14)), "v"(lo32(r18)), "v"(lo32(r41)), "v"(hi32(r14)), "v"(hi32(r18)), "v"(hi32(r41)),         \
+    "v"(lo32(r28)), "v"(lo32(r34)), "v"(lo32(r39)), "v"(hi32(r28)), "v"(hi32(r34)), "v"(hi32(r39)),         \
+    "v"(lo32(e)), "v"(lo32(s[F])), "v"(lo32(s[G])), "v"(hi32(e)), "v"(hi32(s[F])), "v"(hi32(s[G])),         \
+    "v"(lo32(a)), "v"(lo32(s[B])), "v"(lo32(s[C])), "v"(hi32(a)), "v"(hi32(s[B])), "v"(hi32(s[C]))
+    if constexpr (kUnit == 8)
+      asm("s_setprio %32\n\t" BM_GROUP8_ "\n\ts_setprio %33" BM_GROUP8_OPS_, "n"(BM_STEER_LOW), "n"(BM_STEER_BASE));
+    else
+      asm(BM_GROUP8_ BM_GROUP8_OPS_);
+#undef BM_GROUP8_
+#undef BM_GROUP8_OPS_
+    const uint64_t t1 = add64(add64(add64(s[H], opaque(mk64(s1l, s1h))), opaque(mk64(chl, chh))), K(T) + w[T & 15]);
+    s[D] = add64(s[D], t1);
+    s[H] = add64(add64(t1, opaque(mk64(s0l, s0h))), opaque(mk64(mjl, mjh)));
+  } else if constexpr (kUnit == 4) {
+    // Sigma1 with Ch (both of e, T1's terms), then Sigma0 with Maj (both of a): two units of four
+    const uint64_t e = s[E], a = s[A];
+    const uint64_t r14 = rotr<14>(e), r18 = rotr<18>(e), r41 = rotr<41>(e);
+    uint32_t s1l, s1h, chl, chh;
+    asm("s_setprio %16\n\t"
+        "v_bitop3_b32 %0, %4, %5, %6 bitop3:0x96\n\t"
+        "v_bitop3_b32 %1, %7, %8, %9 bitop3:0x96\n\t"
+        "v_bitop3_b32 %2, %10, %11, %12 bitop3:0xca\n\t"
+        "v_bitop3_b32 %3, %13, %14, %15 bitop3:0xca\n\t"
+        "s_setprio %17"
+        : "=&v"(s1l), "=&v"(s1h), "=&v"(chl), "=v"(chh)
+        : "v"(lo32(r14)), "v"(lo32(r18)), "v"(lo32(r41)), "v"(hi32(r14)), "v"(hi32(r18)), "v"(hi32(r41)),
+          "v"(lo32(e)), "v"(lo32(s[F])), "v"(lo32(s[G])), "v"(hi32(e)), "v"(hi32(s[F])), "v"(hi32(s[G])),
+          "n"(BM_STEER_LOW), "n"(BM_STEER_BASE));
+    const uint64_t t1 = add64(add64(add64(s[H], opaque(mk64(s1l, s1h))), opaque(mk64(chl, chh))), K(T) + w[T & 15]);
+    s[D] = add64(s[D], t1);
+    const uint64_t r28 = rotr<28>(a), r34 = rotr<34>(a), r39 = rotr<39>(a);
+    uint32_t s0l, s0h, mjl, mjh;
+    asm("s_setprio %16\n\t"
+        "v_bitop3_b32 %0, %4, %5, %6 bitop3:0x96\n\t"
+        "v_bitop3_b32 %1, %7, %8, %9 bitop3:0x96\n\t"
+        "v_bitop3_b32 %2, %10, %11, %12 bitop3:0xe8\n\t"
+        "v_bitop3_b32 %3, %13, %14, %15 bitop3:0xe8\n\t"
+        "s_setprio %17"
+        : "=&v"(s0l), "=&v"(s0h), "=&v"(mjl), "=v"(mjh)
+        : "v"(lo32(r28)), "v"(lo32(r34)), "v"(lo32(r39)), "v"(hi32(r28)), "v"(hi32(r34)), "v"(hi32(r39)),
+          "v"(lo32(a)), "v"(lo32(s[B])), "v"(lo32(s[C])), "v"(hi32(a)), "v"(hi32(s[B])), "v"(hi32(s[C])),
+          "n"(BM_STEER_LOW), "n"(BM_STEER_BASE));
+    s[H] = add64(add64(t1, opaque(mk64(s0l, s0h))), opaque(mk64(mjl, mjh)));
+  } else {
+    constexpr bool kS = kUnit == 2;
+    const uint64_t t1 = add64(add64(add64(s[H], Sig1<kS>(s[E])), Ch<kS>(s[E], s[F], s[G])), K(T) + w[T & 15]);
+    s[D] = add64(s[D], t1);
+    s[H] = add64(add64(t1, Sig0<kS>(s[A])), Maj<kS>(s[A], s[B], s[C]));
+  }
 }
 
-template <int T, int END, bool kTrial1 = false, bool kVar0 = false>
+template <int T, int END, bool kTrial1 = false, bool kVar0 = false, bool kSearch = false>
 BM_DEV void rounds(uint64_t (&s)[8], uint64_t (&w)[16]) {
   if constexpr (T < END) {
-    round_step<T, kTrial1, kVar0>(s, w);
-    rounds<T + 1, END, kTrial1, kVar0>(s, w);
+    round_step<T, kTrial1, kVar0, kSearch>(s, w);
+    rounds<T + 1, END, kTrial1, kVar0, kSearch>(s, w);
   }
 }
 
@@ -293,6 +406,7 @@ BM_DEV void rounds_kw(uint64_t (&s)[8], const uint64_t* __restrict__ kw) {
 
 // trial(n, ih) with ih given as 8 big-endian words.  Round 0 of each block is folded:
 // from the IV with W0 unknown, a1 = W0 + A1C and e1 = W0 + E1C.
+template <bool kSearch = false>
 BM_DEV uint64_t trial_of(const uint64_t (&ihw)[8], uint64_t nonce) {
   uint64_t w[16];
   w[0] = nonce;
@@ -304,7 +418,7 @@ BM_DEV uint64_t trial_of(const uint64_t (&ihw)[8], uint64_t nonce) {
   w[15] = 72 * 8;
   // state after the folded round 0 (round 1 has A = 7: a=s7 b=s0 c=s1 d=s2 e=s3 f=s4 g=s5 h=s6)
   uint64_t s[8] = {IV(0), IV(1), IV(2), nonce + E1C, IV(4), IV(5), IV(6), nonce + A1C};
-  rounds<1, 80, true>(s, w);
+  rounds<1, 80, true, false, kSearch>(s, w);
 #ifdef BM_TRIAL_MID
   BM_TRIAL_MID();  // A/B hook of the search kernel (bmpow_kernels.hip), nothing elsewhere
 #endif
@@ -317,7 +431,7 @@ BM_DEV uint64_t trial_of(const uint64_t (&ihw)[8], uint64_t nonce) {
   for (int i = 9; i < 15; ++i) w2[i] = 0;
   w2[15] = 64 * 8;
   uint64_t s2[8] = {IV(0), IV(1), IV(2), w2[0] + E1C, IV(4), IV(5), IV(6), w2[0] + A1C};
-  rounds<1, 80>(s2, w2);
+  rounds<1, 80, false, false, kSearch>(s2, w2);
   return s2[0] + IV(0);
 }
 
@@ -325,7 +439,7 @@ BM_DEV uint64_t trial_of(const uint64_t (&ihw)[8], uint64_t nonce) {
 // skipped and *cut is set (the single-object kernel's mid-trial bound check, bmpow_kernels.hip sweep).
 // Kept apart from trial_of: passing the state between two halves through an array made the compiler
 // emit ~105 more VALU per trial in every caller (PMC, profiles/r04/eng6/).
-template <class Stop>
+template <bool kSearch = false, class Stop>
 BM_DEV uint64_t trial_of_cut(const uint64_t (&ihw)[8], uint64_t nonce, Stop&& stop, bool& cut) {
   uint64_t w[16];
   w[0] = nonce;
@@ -336,7 +450,7 @@ BM_DEV uint64_t trial_of_cut(const uint64_t (&ihw)[8], uint64_t nonce, Stop&& st
   for (int i = 10; i < 15; ++i) w[i] = 0;
   w[15] = 72 * 8;
   uint64_t s[8] = {IV(0), IV(1), IV(2), nonce + E1C, IV(4), IV(5), IV(6), nonce + A1C};
-  rounds<1, 80, true>(s, w);
+  rounds<1, 80, true, false, kSearch>(s, w);
   cut = stop();
   if (cut) return ~0ULL;
   uint64_t w2[16];
@@ -348,12 +462,12 @@ BM_DEV uint64_t trial_of_cut(const uint64_t (&ihw)[8], uint64_t nonce, Stop&& st
   w2[15] = 64 * 8;
   uint64_t s2[8] = {IV(0), IV(1), IV(2), w2[0] + E1C, IV(4), IV(5), IV(6), w2[0] + A1C};
 #ifdef BM_CUT2  // A/B variant: a second test halfway through the second compression
-  rounds<1, 40>(s2, w2);
+  rounds<1, 40, false, false, kSearch>(s2, w2);
   cut = stop();
   if (cut) return ~0ULL;
-  rounds<40, 80>(s2, w2);
+  rounds<40, 80, false, false, kSearch>(s2, w2);
 #else
-  rounds<1, 80>(s2, w2);
+  rounds<1, 80, false, false, kSearch>(s2, w2);
 #endif
   return s2[0] + IV(0);
 }

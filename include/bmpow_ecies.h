@@ -20,6 +20,7 @@
 #define BMPOW_ECIES_H
 
 #include "bmpow.h"
+#include "bmpow_seal.h" /* bmpow_aes256_cbc: the raw cipher on the device */
 
 #ifdef __cplusplus
 extern "C" {

@@ -7,7 +7,8 @@
  * for ECIES a fresh key pair (r, R = r G), the shared x(r Q) with the recipient's key Q, SHA-512 of it
  * as key_e || key_m, AES-256-CBC and HMAC-SHA256 (ECC.raw_encrypt, :462-482).  Its addresses' public
  * keys come from highlevelcrypto.pointMult (:111-146).  Here a batch goes through each in one call: the
- * curve and scalar arithmetic on the device, the AES / HMAC pass on the host's threads.
+ * curve and scalar arithmetic on the device, and the AES / HMAC pass either on the host's threads
+ * (libcrypto) or on the device as well (sl_seal_kernel), by bmpow_send_set_seal / BMPOW_SEAL.
  *
  * Same conventions as bmpow_sig.h / bmpow_ecies.h (return codes, bmpow_last_error, thread safety);
  * bmpow_abort() is honoured between launches.  The calls run on the first selected device.  n == 0
@@ -17,6 +18,7 @@
 #define BMPOW_SEND_H
 
 #include "bmpow.h"
+#include "bmpow_seal.h" /* the device seal's calls, the mode knob and its counters */
 #include "bmpow_sig.h"
 
 #ifdef __cplusplus

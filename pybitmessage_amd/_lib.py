@@ -242,6 +242,28 @@ SEND_SIGNATURES = [
     ('bmpow_send_reset_stats', None, []),
 ]
 
+
+class BmpowSealStats(ctypes.Structure):
+    """``bmpow_seal_stats`` (include/bmpow_send.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows_device', ctypes.c_uint64), ('rows_host', ctypes.c_uint64),
+                ('sets', ctypes.c_uint64), ('launches', ctypes.c_uint64), ('seal_kernel_ms', ctypes.c_double),
+                ('pack_ms', ctypes.c_double), ('copy_ms', ctypes.c_double), ('scatter_ms', ctypes.c_double)]
+
+
+# the device seal's entry points (include/bmpow_send.h) and the raw CBC call (include/bmpow_ecies.h)
+SEAL_SIGNATURES = [
+    ('bmpow_ecies_seal_batch', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, _p64,
+      _p64]),
+    ('bmpow_send_set_seal', ctypes.c_int, [ctypes.c_int]),
+    ('bmpow_seal_plan', ctypes.c_int64, [ctypes.c_size_t, _p64, _u64, _u64, _pu32, _p64]),
+    ('bmpow_seal_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowSealStats)]),
+    ('bmpow_seal_reset_stats', None, []),
+    ('bmpow_aes256_cbc', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, _p64, ctypes.c_void_p, _p64,
+      ctypes.POINTER(ctypes.c_int64)]),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -259,7 +281,8 @@ def load(path=None):
         raise BmpowUnavailable(E_NODEV, 'libbmpow_hip.so not built at %s (run __graft_entry__.build() '
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
-    for name, res, args in SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES:
+    for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
+                            SEAL_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -6,7 +6,8 @@
 //     key = SHA512(x(k R)),  key_e = key[:32],  key_m = key[32:]
 //     the key matches iff HMAC_SHA256(key_m, data[:-32]) == data[-32:]
 // Almost every try fails, so the batch computes only the verdict (and key_e of the matching pair); the
-// AES pass of the few matches stays on the host.  Host side: bmpow_host_ecies.hip.
+// AES pass of the few matches is a call of its own (bmpow_aes256_cbc, bmpow_seal.hip).  Host side:
+// bmpow_host_ecies.hip.
 //
 // Three kernels, one lane per object, 64 objects and ONE key per wave:
 //   ec_prep_kernel : per object, once: the on-curve check and the table of odd multiples of R;

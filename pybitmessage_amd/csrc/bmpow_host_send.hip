@@ -1,6 +1,7 @@
 // bmpow_host_send.hip -- the send side's host unit: range checks and random draws, the set loop that takes
 // public keys, signatures and ECIES key agreements through the device, DER encoding, the AES / HMAC pass
-// of the blobs, and the entry points of include/bmpow_send.h.
+// of the blobs -- libcrypto on the host's threads, or the seal kernel behind the ladder
+// (bmpow_host_seal.hip), by bmpow_send_set_seal -- and the entry points of include/bmpow_send.h.
 #include "bmpow_host.h"
 
 #include <openssl/crypto.h>
@@ -9,6 +10,7 @@
 
 #include "../../include/bmpow_send.h"
 #include "bmpow_ecies_kernels.h"
+#include "bmpow_host_seal.h"
 #include "bmpow_send_kernels.h"
 
 // ---------------------------------------------------------------------------------------
@@ -157,6 +159,14 @@ struct SendCall {
   uint8_t* rs = nullptr;   // sign: r || s
   uint8_t* key = nullptr;  // encrypt: key_e || key_m
   uint8_t* ok = nullptr;   // sign: r and s nonzero; encrypt: the recipient key is on the curve
+  // encrypt, sealed on the device: the derived keys and the points stay there (xy, key and ok are not
+  // written); the blobs go straight to outs / out_lens, 0 for a recipient key off the curve
+  bool seal = false;
+  const uint8_t* const* plains = nullptr;
+  const uint64_t* lens = nullptr;
+  const uint8_t* ivs = nullptr;
+  uint8_t* const* outs = nullptr;
+  uint64_t* out_lens = nullptr;
 };
 
 int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
@@ -164,6 +174,19 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
   if (hashing)
     std::stable_sort(rows.begin(), rows.end(),
                      [&](uint32_t a, uint32_t b) { return msg_blocks(c.msg_lens[a]) > msg_blocks(c.msg_lens[b]); });
+  // the seal's sets: the rows by AES block count, descending, cut by the planner (rows and pool bytes)
+  std::vector<uint64_t> seal_slot, seal_off;
+  std::vector<uint32_t> seal_set_of;
+  uint64_t seal_max_pool = 16;
+  if (c.seal) {
+    std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return c.lens[a] / 16 > c.lens[b] / 16; });
+    seal_slot.resize(rows.size()), seal_off.resize(rows.size()), seal_set_of.resize(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) seal_slot[i] = bmseal::seal_slot_bytes(c.lens[rows[i]]);
+    if (bmseal::plan_slots(rows.size(), seal_slot.data(), kSendSetRows, kSendSetPoolBytes, seal_set_of.data(),
+                           seal_off.data()) < 0)
+      return set_err(BMPOW_E_ARG, "seal plan refused");
+    for (size_t i = 0; i < rows.size(); ++i) seal_max_pool = std::max(seal_max_pool, seal_off[i] + seal_slot[i]);
+  }
   Shard& sh = g_shards[0];
   HIPTRY(hipSetDevice(sh.dev));
   const ec::ge* comb = nullptr;
@@ -178,7 +201,12 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
   Wiped<uint64_t> kout;
   kw.v.resize(cap);
   if (c.mode == kModeSign) d.v.resize(cap);
-  if (c.mode == kModeEncrypt) kout.v.resize(8 * cap_stride);
+  if (c.mode == kModeEncrypt && !c.seal) kout.v.resize(8 * cap_stride);
+  SealIo sio;
+  if (c.seal) {
+    if (const int rc = sio.init(sh.dev, cap, seal_max_pool); rc < 0) return rc;
+    g_seal_stats.calls++;
+  }
   // the device buffers that hold secrets, sized once for the largest set: a later growth would free an
   // unwiped one
   HIPTRY(b.kw.alloc(sh.dev, cap_stride));
@@ -200,6 +228,7 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
     while (i1 < rows.size() && i1 - i0 < kSendSetRows) {
       const uint32_t nb = hashing ? msg_blocks(c.msg_lens[rows[i1]]) : 0;
       if (i1 != i0 && (blocks + nb) * 64 > kSendSetPoolBytes) break;
+      if (c.seal && seal_set_of[i1] != seal_set_of[i0]) break;
       blocks += nb;
       ++i1;
     }
@@ -284,6 +313,13 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
       ok8.resize(n);
       HIPTRY(hipMemcpyAsync(rs.data(), b.rs.get(), rs.size() * sizeof(sc), hipMemcpyDeviceToHost, sh.stream));
       HIPTRY(hipMemcpyAsync(ok8.data(), b.ok8.get(), n, hipMemcpyDeviceToHost, sh.stream));
+    } else if (c.seal) {
+      SealSet s;
+      s.n = n, s.stride = stride;
+      s.row = rows.data() + i0, s.off = seal_off.data() + i0;
+      s.pool_bytes = seal_off[i1 - 1] + seal_slot[i1 - 1];
+      s.plains = c.plains, s.lens = c.lens, s.ivs = c.ivs, s.outs = c.outs, s.out_lens = c.out_lens;
+      if (const int rc = seal_set(sh, sio, s, b.kout.get(), b.pt.get(), b.ok32.get()); rc < 0) return rc;
     } else {
       pt.resize(n);
       HIPTRY(hipMemcpyAsync(pt.data(), b.pt.get(), n * sizeof(ec::ge), hipMemcpyDeviceToHost, sh.stream));
@@ -299,7 +335,7 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
     if (const int rc = send_elapsed(g_send_stats.comb_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
     if (const int rc = send_elapsed(g_send_stats.scalar_ms, b.ev[2], b.ev[3]); rc < 0) return rc;
     if (const int rc = send_elapsed(g_send_stats.ladder_ms, b.ev[3], b.ev[4]); rc < 0) return rc;
-    for (uint32_t j = 0; j < n; ++j) {
+    for (uint32_t j = 0; j < n && !c.seal; ++j) {
       const size_t row = rows[i0 + j];
       if (c.mode == kModeSign) {
         c.ok[row] = ok8[j] ? 1 : 0;
@@ -571,21 +607,34 @@ int bmpow_ecies_encrypt(size_t n, const uint8_t* const* plains, const uint64_t* 
     if (!draw_bytes(iv_drawn.data(), iv_drawn.size())) return set_err(BMPOW_E_ARG, "RAND_bytes failed");
     ivs = iv_drawn.data();
   }
-  key.v.resize(64 * n);
-  std::vector<uint8_t> R(64 * n), ok(n, 0);
-  std::vector<uint32_t> rows;
+  // Device mode: the rows up to the protocol's object size are sealed by the kernel behind their ladder;
+  // a longer one takes the host's path below, as every row does in host mode.
+  const bool device = seal_mode() == 1;
+  std::vector<uint8_t> R, ok(n, 0);
+  std::vector<uint32_t> rows, sealed;
   rows.reserve(n);
   for (size_t i = 0; i < n; ++i)
     if (coord_in_range(sc_from_be(pubkeys + 64 * i)) && coord_in_range(sc_from_be(pubkeys + 64 * i + 32)))
-      rows.push_back((uint32_t)i);
+      (device && lens[i] <= bmseal::kDevicePlain ? sealed : rows).push_back((uint32_t)i);
   SendCall c;
   c.mode = kModeEncrypt;
   c.scalars = ephem ? ephem : drawn.v.data();
   c.pubkeys = pubkeys;
+  if (!sealed.empty()) {
+    SendCall d = c;
+    d.seal = true;
+    d.plains = plains, d.lens = lens, d.ivs = ivs, d.outs = outs, d.out_lens = out_lens;
+    if (const int rc = run_rows(d, sealed); rc < 0) return rc;
+    if (!rows.empty()) g_send_stats.calls--;  // one call, though its rows took two trips through the set loop
+  }
+  if (rows.empty()) return 0;
+  key.v.resize(64 * n);
+  R.resize(64 * n);
   c.xy = R.data();
   c.key = key.v.data();
   c.ok = ok.data();
   if (const int rc = run_rows(c, rows); rc < 0) return rc;
+  if (device) g_seal_stats.rows_host += rows.size();
   const auto t_seal = std::chrono::steady_clock::now();
   std::atomic<bool> failed{false};
   bmsched::parallel_for(n, 256, [&](size_t a, size_t z) {

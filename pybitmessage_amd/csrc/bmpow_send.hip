@@ -6,7 +6,8 @@
 //     encrypt:  R = t G,  key = SHA512(x(t Q)),  key_e = key[:32], key_m = key[32:]
 //                                                               (ECC.raw_encrypt, :462-482)
 // The receive side's arithmetic composed the other way round (bmpow_sig.hip, bmpow_ecies.hip).  The AES
-// and HMAC pass stays on the host.  Host side: bmpow_host_send.hip.
+// and HMAC pass is bmpow_seal.hip's kernel behind these, or libcrypto on the host.  Host side:
+// bmpow_host_send.hip.
 //
 // One lane per row, the phases as separate kernels so that no phase's register allocation carries
 // another's state:

@@ -6,7 +6,8 @@ The reference tries every msg that passed the PoW check against every private ke
 secp256k1 with the message's ephemeral key, a SHA-512 of the shared x and an HMAC-SHA256 over the
 whole blob -- and almost every try fails.  Here ``bmpow_ecies_match`` (``include/bmpow_ecies.h``)
 runs all tries of a batch on the device and reports, per payload, the key whose MAC verifies; the
-AES pass of the few matches runs on the host (``bmpow_ecies_decrypt``, libcrypto).  Every key is
+AES pass of the matches is one more call on the device (``bmpow_aes256_cbc``; a single payload can
+still be opened on the host with ``bmpow_ecies_decrypt``, libcrypto).  Every key is
 tried against every payload whatever the outcome, so a call's duration says nothing about which
 payload matched.  No CPU fallback: without the HIP library the calls raise
 :class:`BmpowUnavailable`.
@@ -64,15 +65,58 @@ def decrypt(payload, key_e):
     return out.raw[:n] if n >= 0 else None
 
 
+def aes_cbc_batch(keys, ivs, data, decrypt=False):
+    """Raw AES-256-CBC with PKCS#7 padding on the device (``bmpow_aes256_cbc``), one 32-byte key and one
+    16-byte IV per message.  Encrypting gives the padded ciphertexts.  Decrypting gives the plaintexts,
+    None where the reference's ``decrypt`` raises: an input that is empty or no multiple of 16 bytes, or
+    bad padding."""
+    n = len(data)
+    if not (n == len(keys) == len(ivs)):
+        raise ValueError('one key and one IV per message')
+    if n == 0:
+        return []
+    ks, vs = [bytes(k) for k in keys], [bytes(v) for v in ivs]
+    if any(len(k) != 32 for k in ks) or any(len(v) != 16 for v in vs):
+        raise ValueError('keys are 32 bytes, IVs 16 each')
+    msgs = [d if type(d) is bytes else bytes(d) for d in data]
+    lib = _lib.get()
+    ptrs = (ctypes.c_char_p * n)(*msgs)
+    lens = np.fromiter(map(len, msgs), dtype=np.uint64, count=n)
+    caps = lens.copy() if decrypt else 16 * (lens // 16 + 1)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(caps, out=offs[1:])
+    arena = np.zeros(max(int(offs[-1]), 1), dtype=np.uint8)
+    outs = (arena.ctypes.data + offs[:-1]).astype(np.uint64)
+    got = np.zeros(n, dtype=np.int64)
+    p64 = ctypes.POINTER(ctypes.c_uint64)
+    _lib.check(lib, lib.bmpow_aes256_cbc(n, 1 if decrypt else 0, b''.join(ks), b''.join(vs),
+                                         ctypes.cast(ptrs, ctypes.c_void_p), lens.ctypes.data_as(p64),
+                                         outs.ctypes.data_as(ctypes.c_void_p), caps.ctypes.data_as(p64),
+                                         got.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               'bmpow_aes256_cbc')
+    return [arena[int(offs[i]):int(offs[i]) + int(got[i])].tobytes() if got[i] >= 0 else None for i in range(n)]
+
+
 def decrypt_batch(payloads, privkeys):
     """Per payload ``(index, plaintext)`` of the matching key, or None where no key matches or the
     matching key's plaintext has bad padding (the reference's ``decrypt`` raises there and
-    ``processmsg`` goes on as if the key did not match)."""
+    ``processmsg`` goes on as if the key did not match).  The matches' ciphertexts are opened in one
+    ``bmpow_aes256_cbc`` call on the device."""
     match, key_e, objs = _match(payloads, privkeys, True)
-    out = []
-    for i, m in enumerate(match):
-        plain = decrypt(objs[i], key_e[i].tobytes()) if m is not None else None
-        out.append((m, plain) if plain is not None else None)
+    hit = [i for i, m in enumerate(match) if m is not None]
+    out = [None] * len(match)
+    if not hit:
+        return out
+    # a match is well-formed: its header lies inside data[:-32] (ecies_parse), the ciphertext behind it
+    bodies = []
+    for i in hit:
+        p = objs[i]
+        xl = int.from_bytes(p[18:20], 'big')
+        bodies.append(p[22 + xl + int.from_bytes(p[20 + xl:22 + xl], 'big'):-32])
+    plains = aes_cbc_batch([key_e[i].tobytes() for i in hit], [objs[i][:16] for i in hit], bodies, decrypt=True)
+    for i, plain in zip(hit, plains):
+        if plain is not None:
+            out[i] = (match[i], plain)
     return out
 
 

@@ -5,7 +5,9 @@ The reference signs and encrypts every object it sends with ``highlevelcrypto.si
 its addresses' public keys with ``pointMult`` / ``privToPub`` (``:47-51``, ``:111-146``): one
 ``pyelliptic`` call per object.  Here ``bmpow_sig_sign``, ``bmpow_ecies_encrypt`` and
 ``bmpow_ec_pubkeys`` (``include/bmpow_send.h``) take a whole batch: the curve and scalar arithmetic run
-on the device, the AES-256-CBC and HMAC-SHA256 pass of the blobs on the host's threads (libcrypto).
+on the device, the AES-256-CBC and HMAC-SHA256 pass of the blobs on the host's threads (libcrypto) or,
+with :func:`set_seal` (``BMPOW_SEAL=device``), on the device behind the ladder (``sl_seal_kernel``),
+where the derived keys never reach host memory; the blobs are the same bytes either way.
 Nonces, ephemeral keys and IVs come from libcrypto's ``RAND_bytes`` unless the caller supplies them.  No
 CPU fallback: without the HIP library the calls raise :class:`BmpowUnavailable`.
 """
@@ -126,6 +128,61 @@ def seal(plaintext, iv, R_xy, key):
     return out.raw[:n]
 
 
+def _arena(lens):
+    """One output buffer for blobs of ``lens``-byte plaintexts: (arena, offsets, pointers, capacities)."""
+    m = len(lens)
+    caps = 118 + 16 * (lens // 16 + 1)
+    offs = np.zeros(m + 1, dtype=np.uint64)
+    np.cumsum(caps, out=offs[1:])
+    arena = np.zeros(int(offs[-1]), dtype=np.uint8)
+    ptrs = (arena.ctypes.data + offs[:-1]).astype(np.uint64)
+    return arena, offs, ptrs, caps
+
+
+def seal_batch(plaintexts, ivs, R_xys, keys):
+    """:func:`seal` for a batch on the device (``bmpow_ecies_seal_batch``): per row the blob for its
+    16-byte IV, ephemeral public key ``X || Y`` (64 bytes, taken as they are) and ``key_e || key_m``
+    (64 bytes) -- the bytes :func:`seal` gives."""
+    n = len(plaintexts)
+    if not (n == len(ivs) == len(R_xys) == len(keys)):
+        raise ValueError('one IV, one point and one key per plaintext')
+    if n == 0:
+        return []
+    pts = _as_bytes(plaintexts)
+    iv, pub, key = b''.join(_as_bytes(ivs)), b''.join(_as_bytes(R_xys)), b''.join(_as_bytes(keys))
+    if len(iv) != 16 * n or len(pub) != 64 * n or len(key) != 64 * n or any(len(k) != 64 for k in keys) \
+            or any(len(v) != 16 for v in ivs) or any(len(r) != 64 for r in R_xys):
+        raise ValueError('the IV is 16 bytes, the point and the key 64 each')
+    lib = _lib.get()
+    pp = (ctypes.c_char_p * n)(*pts)
+    lens = np.fromiter(map(len, pts), dtype=np.uint64, count=n)
+    arena, offs, ptrs, caps = _arena(lens)
+    got = np.zeros(n, dtype=np.uint64)
+    _lib.check(lib, lib.bmpow_ecies_seal_batch(n, ctypes.cast(pp, ctypes.c_void_p), lens.ctypes.data_as(_P64), iv, pub, key,
+                                               ptrs.ctypes.data_as(ctypes.c_void_p), caps.ctypes.data_as(_P64),
+                                               got.ctypes.data_as(_P64)),
+               'bmpow_ecies_seal_batch')
+    return [arena[int(offs[j]):int(offs[j]) + int(got[j])].tobytes() for j in range(n)]
+
+
+def set_seal(mode):
+    """Where :func:`encrypt_batch` seals its blobs (``bmpow_send_set_seal``): 0 on the host's threads, 1 on
+    the device, -1 only asks.  Returns the previous mode.  No device is touched."""
+    return _lib.host().bmpow_send_set_seal(int(mode))
+
+
+def seal_stats():
+    """The device seal's counters (``bmpow_seal_stats``) as a dict."""
+    lib = _lib.host()
+    st = _lib.BmpowSealStats()
+    _lib.check(lib, lib.bmpow_seal_get_stats(ctypes.byref(st)), 'bmpow_seal_get_stats')
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def reset_seal_stats():
+    _lib.host().bmpow_seal_reset_stats()
+
+
 def encrypt_batch(plaintexts, pubkeys, ephemeral=None, ivs=None):
     """``highlevelcrypto.encrypt`` for a batch: the ECIES blob of each plaintext to its recipient key
     (64 or 65 raw bytes or their hex, as ``signatures.verify_batch`` takes keys).  None where the
@@ -148,11 +205,7 @@ def encrypt_batch(plaintexts, pubkeys, ephemeral=None, ivs=None):
     lib = _lib.get()
     pp = (ctypes.c_char_p * m)(*[pts[i] for i in live])
     lens = np.fromiter((len(pts[i]) for i in live), dtype=np.uint64, count=m)
-    caps = 118 + 16 * (lens // 16 + 1)
-    offs = np.zeros(m + 1, dtype=np.uint64)
-    np.cumsum(caps, out=offs[1:])
-    arena = np.zeros(int(offs[-1]), dtype=np.uint8)
-    ptrs = (arena.ctypes.data + offs[:-1]).astype(np.uint64)
+    arena, offs, ptrs, caps = _arena(lens)
     got = np.zeros(m, dtype=np.uint64)
     _lib.check(lib, lib.bmpow_ecies_encrypt(m, ctypes.cast(pp, ctypes.c_void_p), lens.ctypes.data_as(_P64),
                                             b''.join(keys[i] for i in live), eph, iv,

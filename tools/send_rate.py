@@ -18,7 +18,16 @@ most), each for --cpu-seconds: SHA-256 + ``ECDSA_sign`` (src/pyelliptic/ecc.py:3
 generated key pair, ``ECDH_compute_key``, SHA-512, AES-256-CBC and HMAC-SHA256 (:462-482).
 
 Prints one JSON line.  Without a device the GPU leg raises (there is no fallback); --cpu-only runs the
-CPU leg alone."""
+CPU leg alone.
+
+    python tools/send_rate.py --rows 500000 --len 200 --seal both --out profiles/send/seal_ab_l200.json
+
+--seal host|device|both measures ``bmpow_ecies_encrypt`` alone with the blobs sealed on the host's threads or
+by the seal kernel (``bmpow_send_set_seal``): under the same seeded ephemeral keys and IVs, each mode warmed,
+then --reps timed calls each (three at least), the modes taking turns in one process.  The JSON holds every
+repetition's wall time, the per-call split of ``bmpow_send_stats`` and ``bmpow_seal_stats``, a byte-for-byte
+comparison of the two modes' blobs, and the verdict of the rule that decides the library's default: the device
+mode's median must beat the host mode's by more than the spread of the host's own repetitions and by 1 %."""
 import argparse
 import ctypes
 import ctypes.util
@@ -139,6 +148,82 @@ def gpu_leg(msgs, privs, pubs, reps):
     return res
 
 
+def seal_ab(msgs, privs, pubs, reps, which):
+    """``bmpow_ecies_encrypt`` under each seal mode in turn, same seeded ephemeral keys and IVs."""
+    import numpy as np
+    from pybitmessage_amd import _lib, ecies
+    lib = _lib.get()
+    n = len(msgs)
+    reps = max(3, reps)
+    p64, pu8 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8)
+    rng = np.random.default_rng(20261020)
+    eph = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    eph[:, 0] &= 0x7f  # below the group order
+    eph[:, 31] |= 1    # and not zero
+    ivs = rng.integers(0, 256, size=(n, 16), dtype=np.uint8)
+    mp = (ctypes.c_char_p * n)(*msgs)
+    ml = np.fromiter(map(len, msgs), dtype=np.uint64, count=n)
+    qk = b''.join(pubs)
+    caps = 118 + 16 * (ml // 16 + 1)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(caps, out=offs[1:])
+    modes = {'host': 0, 'device': 1}
+    names = ['host', 'device'] if which == 'both' else [which]
+    arena = {m: np.zeros(int(offs[-1]), dtype=np.uint8) for m in names}
+    got = {m: np.zeros(n, dtype=np.uint64) for m in names}
+
+    def call(m):
+        outs = (arena[m].ctypes.data + offs[:-1]).astype(np.uint64)
+        lib.bmpow_send_set_seal(modes[m])
+        t0 = time.perf_counter()
+        _lib.check(lib, lib.bmpow_ecies_encrypt(n, ctypes.cast(mp, ctypes.c_void_p), ml.ctypes.data_as(p64), qk,
+                                                eph.ctypes.data_as(ctypes.c_char_p), ivs.ctypes.data_as(ctypes.c_char_p),
+                                                outs.ctypes.data_as(ctypes.c_void_p), caps.ctypes.data_as(p64),
+                                                got[m].ctypes.data_as(p64)), 'bmpow_ecies_encrypt')
+        return time.perf_counter() - t0
+
+    first = lib.bmpow_send_set_seal(-1)
+    res = {m: {'wall_s': [], 'send': {}, 'seal': {}} for m in names}
+    try:
+        for m in names:
+            call(m)  # warm-up: the same shapes (and the comb table's build)
+        for _ in range(reps):
+            for m in names:
+                lib.bmpow_send_reset_stats()
+                lib.bmpow_seal_reset_stats()
+                res[m]['wall_s'].append(round(call(m), 5))
+                st, sl = _lib.BmpowSendStats(), _lib.BmpowSealStats()
+                _lib.check(lib, lib.bmpow_send_get_stats(ctypes.byref(st)), 'bmpow_send_get_stats')
+                _lib.check(lib, lib.bmpow_seal_get_stats(ctypes.byref(sl)), 'bmpow_seal_get_stats')
+                for f in ('comb_ms', 'scalar_ms', 'ladder_ms', 'seal_ms', 'host_ms'):
+                    res[m]['send'].setdefault(f, []).append(round(getattr(st, f), 3))
+                for f, _ in sl._fields_:
+                    res[m]['seal'].setdefault(f, []).append(round(getattr(sl, f), 3))
+    finally:
+        lib.bmpow_send_set_seal(first)
+    out = {'reps': reps, 'default_mode': 'device' if first else 'host', 'modes': res}
+    for m in names:
+        w = sorted(res[m]['wall_s'])
+        res[m]['median_s'] = w[len(w) // 2] if len(w) % 2 else (w[len(w) // 2 - 1] + w[len(w) // 2]) / 2
+        res[m]['spread_s'] = round(w[-1] - w[0], 5)
+        res[m]['blobs_made'] = int(np.count_nonzero(got[m]))
+    pick = list(range(0, n, max(1, n // 256)))[:256]
+    m0 = names[-1]
+    blobs = [arena[m0][int(offs[i]):int(offs[i]) + int(got[m0][i])].tobytes() for i in pick]
+    if ecies.decrypt_batch(blobs, privs[:KEYS]) != [(i % KEYS, msgs[i]) for i in pick]:
+        raise SystemExit('bmpow_ecies_match / decrypt does not open a blob bmpow_ecies_encrypt (%s) made' % m0)
+    if which == 'both':
+        same = bool(np.array_equal(got['host'], got['device']) and np.array_equal(arena['host'], arena['device']))
+        h, d = res['host'], res['device']
+        gain = h['median_s'] - d['median_s']
+        out['blobs_identical'] = same
+        out['blob_bytes_compared'] = int(got['host'].sum())
+        out['device_gain_s'] = round(gain, 5)
+        out['device_gain_pct'] = round(100 * gain / h['median_s'], 2)
+        out['device_wins'] = bool(same and gain > h['spread_s'] and gain >= 0.01 * h['median_s'])
+    return out
+
+
 def _cpu_worker(args):
     kind, msgs, privs, pubs, seconds = args
     lc = libcrypto()
@@ -203,9 +288,20 @@ def main():
     ap.add_argument('--cpu-seconds', type=float, default=3.0)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--cpu-only', action='store_true')
+    ap.add_argument('--seal', choices=('host', 'device', 'both'),
+                    help='measure bmpow_ecies_encrypt alone under this seal mode (both: A/B in one process)')
+    ap.add_argument('--out', help='with --seal: also write the JSON to this file')
     a = ap.parse_args()
     msgs, privs, pubs = make_inputs(a.rows, a.length)
     out = {'rows': a.rows, 'len': a.length}
+    if a.seal:
+        out['seal_ab'] = seal_ab(msgs, privs, pubs, a.reps, a.seal)
+        if a.out:
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
+                f.write('\n')
+        print(json.dumps(out))
+        return
     if not a.cpu_only:
         out['gpu'] = gpu_leg(msgs, privs, pubs, a.reps)
     if not a.no_cpu:

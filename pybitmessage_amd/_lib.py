@@ -264,6 +264,27 @@ SEAL_SIGNATURES = [
       ctypes.POINTER(ctypes.c_int64)]),
 ]
 
+
+class BmpowIdentRec(ctypes.Structure):
+    """``bmpow_ident_rec`` (include/bmpow_ident.h): one row of the sender identification, 180 bytes."""
+    _fields_ = [('ripe', ctypes.c_uint8 * 20), ('key_v3', ctypes.c_uint8 * 32), ('tag_key', ctypes.c_uint8 * 32),
+                ('tag', ctypes.c_uint8 * 32), ('addr_len', ctypes.c_uint8), ('addr', ctypes.c_char * 63)]
+
+
+class BmpowIdentStats(ctypes.Structure):
+    """``bmpow_ident_stats`` (include/bmpow_ident.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('sets', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('kernel_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_ident.h declares
+IDENT_SIGNATURES = [
+    ('bmpow_ident_derive', ctypes.c_int, [ctypes.c_size_t, ctypes.c_void_p, _p64, _p64, ctypes.c_void_p]),
+    ('bmpow_ident_from_ripe', ctypes.c_int, [ctypes.c_size_t, ctypes.c_void_p, _p64, _p64, ctypes.c_void_p]),
+    ('bmpow_ident_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowIdentStats)]),
+    ('bmpow_ident_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -282,7 +303,7 @@ def load(path=None):
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
-                            SEAL_SIGNATURES):
+                            SEAL_SIGNATURES + IDENT_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -8,6 +8,7 @@ every message in one pass, the scalars mod the group order, and one variable-bas
 signature that serves both digests.  No CPU fallback: without the HIP library the calls raise
 :class:`BmpowUnavailable`.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -207,3 +208,135 @@ def msg_signed_parts(obj, plaintext):
     pos += siglen[1]
     signed = obj[8:20] + encodeVarint(1) + encodeVarint(claimed[0]) + data[:bottom]
     return signed, data[pos:pos + siglen[0]], key
+
+
+BroadcastParts = collections.namedtuple('BroadcastParts', [
+    'signedData', 'signature', 'pubSigningKey64', 'pubEncryptionKey64', 'senderVersion', 'senderStream', 'encoding',
+    'message', 'pubkeyData'])
+PubkeyV4Parts = collections.namedtuple('PubkeyV4Parts', [
+    'signedData', 'signature', 'pubSigningKey64', 'pubEncryptionKey64', 'storedData', 'addressVersion', 'stream', 'tag'])
+
+
+def broadcast_header(obj):
+    """``(broadcastVersion, stream, tag, payloadOffset)`` of a broadcast object as ``processbroadcast``
+    walks it (``src/class_objectProcessor.py:756-769``, ``:808-809``): ``tag`` is the 32 bytes behind the
+    stream number of a v5 broadcast (fewer where the object ends there) and None for v4; the encrypted
+    part is ``obj[payloadOffset:]`` and the signed data starts with ``obj[8:payloadOffset]``.  None where
+    the reference returns at ``:760`` (a broadcast version other than 4 or 5) or a varint raises."""
+    obj = bytes(obj)
+    pos = 20
+    bv = _varint(obj[pos:pos + 9])
+    if bv is None or bv[0] < 4 or bv[0] > 5:
+        return None
+    pos += bv[1]
+    stream = _varint(obj[pos:pos + 10])
+    if stream is None:
+        return None
+    pos += stream[1]
+    if bv[0] == 4:
+        return 4, stream[0], None, pos
+    return 5, stream[0], obj[pos:pos + 32], pos + 32
+
+
+def broadcast_signed_parts(obj, plaintext):
+    """What ``processbroadcast`` reads out of a decrypted broadcast (``src/class_objectProcessor.py:
+    826-915``) as a :class:`BroadcastParts`: ``signedData`` is ``obj[8:payloadOffset] +
+    plaintext[:readPositionAtBottomOfMessage]``, ``pubkeyData`` is ``plaintext[:endOfPubkeyPosition]``
+    (what the pubkeys table stores), the keys are the 64 bytes the reference puts ``04`` in front of.  None
+    where the reference returns before ``verify`` for a reason the plaintext alone decides: a sender
+    version outside 2..3 for a v4 broadcast (``:830``) or below 4 for a v5 one (``:838``), a sender stream
+    other than the object's (``:848``), encoding type 0 (``:901``), or a varint that raises.  The ripe
+    (``:882``) and tag (``:893``) comparisons stay with the caller (:func:`receive.process_broadcasts`).
+    Slices cut short by the end of the plaintext are returned as they are sliced there."""
+    head = broadcast_header(obj)
+    if head is None:
+        return None
+    obj, data = bytes(obj), bytes(plaintext)
+    bv, cleartext_stream = head[0], head[1]
+    pos = 0
+    ver = _varint(data[pos:pos + 9])
+    if ver is None:
+        return None
+    if (bv == 4 and (ver[0] < 2 or ver[0] > 3)) or (bv == 5 and ver[0] < 4):
+        return None
+    pos += ver[1]
+    stream = _varint(data[pos:pos + 9])
+    if stream is None or stream[0] != cleartext_stream:
+        return None
+    pos += stream[1] + 4
+    key_s = data[pos:pos + 64]
+    pos += 64
+    key_e = data[pos:pos + 64]
+    pos += 64
+    if ver[0] >= 3:
+        for _ in range(2):  # requiredAverageProofOfWorkNonceTrialsPerByte, requiredPayloadLengthExtraBytes
+            v = _varint(data[pos:pos + 10])
+            if v is None:
+                return None
+            pos += v[1]
+    end_of_pubkey = pos
+    enc = _varint(data[pos:pos + 9])
+    if enc is None or enc[0] == 0:
+        return None
+    pos += enc[1]
+    mlen = _varint(data[pos:pos + 9])
+    if mlen is None:
+        return None
+    pos += mlen[1]
+    message = data[pos:pos + mlen[0]]
+    pos += mlen[0]
+    bottom = pos
+    siglen = _varint(data[pos:pos + 9])
+    if siglen is None:
+        return None
+    pos += siglen[1]
+    return BroadcastParts(obj[8:head[3]] + data[:bottom], data[pos:pos + siglen[0]], key_s, key_e, ver[0], stream[0],
+                          enc[0], message, data[:end_of_pubkey])
+
+
+def pubkey_v4_header(obj):
+    """``(addressVersion, stream, tag, payloadOffset)`` of an encrypted pubkey object as
+    ``decryptAndCheckPubkeyPayload`` walks it (``src/protocol.py:412-439``); None where a varint raises."""
+    obj = bytes(obj)
+    pos = 20
+    ver = _varint(obj[pos:pos + 10])
+    if ver is None:
+        return None
+    pos += ver[1]
+    stream = _varint(obj[pos:pos + 10])
+    if stream is None:
+        return None
+    pos += stream[1]
+    return ver[0], stream[0], obj[pos:pos + 32], pos + 32
+
+
+def pubkey_v4_signed_parts(obj, plaintext):
+    """What ``decryptAndCheckPubkeyPayload`` reads out of a decrypted v4 pubkey (``src/protocol.py:
+    412-482``) as a :class:`PubkeyV4Parts`: ``signedData`` is ``obj[8:payloadOffset] +
+    plaintext[:endOfKeys]``, ``storedData`` ``obj[20:tagOffset] + plaintext[:endOfKeys]`` (what the pubkeys
+    table stores, ``:421``, ``:477``).  None where a varint raises
+    (the reference's ``except varintDecodeError`` returns ``'failed'``).  The version, stream and ripe
+    comparisons stay with the caller (:func:`receive.check_pubkeys_v4`)."""
+    head = pubkey_v4_header(obj)
+    if head is None:
+        return None
+    obj = bytes(obj)
+    ver, stream, tag, off = head
+    data = bytes(plaintext)
+    pos = 4
+    key_s = data[pos:pos + 64]
+    pos += 64
+    key_e = data[pos:pos + 64]
+    pos += 64
+    for _ in range(2):  # specifiedNonceTrialsPerByte, specifiedPayloadLengthExtraBytes
+        v = _varint(data[pos:pos + 10])
+        if v is None:
+            return None
+        pos += v[1]
+    end = pos
+    siglen = _varint(data[pos:pos + 10])
+    if siglen is None:
+        return None
+    pos += siglen[1]
+    return PubkeyV4Parts(obj[8:off] + data[:end], data[pos:pos + siglen[0]], key_s, key_e, obj[20:off - 32] + data[:end],
+                         ver, stream, tag)

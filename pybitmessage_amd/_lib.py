@@ -285,6 +285,38 @@ IDENT_SIGNATURES = [
     ('bmpow_ident_reset_stats', None, []),
 ]
 
+
+
+class BmpowRxMsgRec(ctypes.Structure):
+    """``bmpow_rx_msg_rec`` (include/bmpow_rx.h): one processed msg, 208 bytes."""
+    _fields_ = [('sender_version', ctypes.c_uint64), ('sender_stream', ctypes.c_uint64), ('ntpb', ctypes.c_uint64),
+                ('extra', ctypes.c_uint64), ('encoding', ctypes.c_uint64), ('claimed_stream', ctypes.c_uint64),
+                ('end_of_pubkey', ctypes.c_uint32), ('msg_off', ctypes.c_uint32), ('msg_len', ctypes.c_uint32),
+                ('ack_off', ctypes.c_uint32), ('ack_len', ctypes.c_uint32), ('sig_off', ctypes.c_uint32),
+                ('sig_len', ctypes.c_uint32), ('bottom', ctypes.c_uint32), ('status', ctypes.c_int32),
+                ('ripe', ctypes.c_uint8 * 20), ('sig_hash', ctypes.c_uint8 * 32), ('addr_len', ctypes.c_uint8),
+                ('addr', ctypes.c_char * 63), ('behaviour', ctypes.c_uint8 * 4), ('digest', ctypes.c_uint8),
+                ('prefix_len', ctypes.c_uint8), ('reserved', ctypes.c_uint8 * 2)]
+
+
+class BmpowRxStats(ctypes.Structure):
+    """``bmpow_rx_stats`` (include/bmpow_rx.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('sets', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('walk_ms', ctypes.c_double), ('hash_ms', ctypes.c_double),
+                ('scalar_ms', ctypes.c_double), ('curve_ms', ctypes.c_double), ('ident_ms', ctypes.c_double),
+                ('finish_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_rx.h declares
+RX_SIGNATURES = [
+    ('bmpow_rx_msgs', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p, _p64, ctypes.c_char_p, ctypes.c_void_p]),
+    ('bmpow_rx_walk_msg', ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(BmpowRxMsgRec)]),
+    ('bmpow_rx_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowRxStats)]),
+    ('bmpow_rx_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -303,7 +335,7 @@ def load(path=None):
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
-                            SEAL_SIGNATURES + IDENT_SIGNATURES):
+                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -3,8 +3,7 @@
 #include "bmpow_host.h"
 
 #include "../../include/bmpow_sig.h"
-#include "bmpow_ecies_kernels.h"
-#include "bmpow_sig_kernels.h"
+#include "bmpow_host_sig.h"
 
 // ---------------------------------------------------------------------------------------
 // One call: the signatures that parse and whose key coordinates are below p, sorted by their message's
@@ -16,9 +15,6 @@
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
 namespace {
-
-constexpr size_t kSigSetObjects = 1u << 18;  // as the ECIES sets: 4,096 waves, 128 MB of key tables
-constexpr size_t kSigSetPoolBytes = 256ull << 20;
 
 using sn::sc;
 
@@ -87,26 +83,6 @@ void pad_blocks(const uint8_t* data, size_t len, uint8_t* dst, uint32_t nblk) {
 }
 
 bmpow_sig_stats g_sig_stats{};  // under g_mu
-
-struct SigBufs {  // one call's buffers on the device
-  DevBuf<sg_sig> sigs;
-  DevBuf<uint4> pool;
-  DevBuf<sc> e;
-  DevBuf<sg_kw> u1;
-  DevBuf<int8_t> dig;
-  DevBuf<uint8_t> flip, tinf, verdict;
-  DevBuf<ec::ge> pts, tab;
-  DevBuf<uint32_t> ok;
-  DevBuf<sg_pt> T;
-  Event ev[4];
-};
-
-int sig_elapsed(double& acc, const Event& a, const Event& b) {
-  float ms = 0;
-  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
-  acc += ms;
-  return 0;
-}
 
 struct SigItem {  // a signature that goes to the device
   uint32_t orig;

@@ -1,4 +1,11 @@
-"""Broadcasts and v4 pubkeys from bytes to a final verdict, with no per-object cryptography in Python.
+"""Msgs, broadcasts and v4 pubkeys from bytes to a final verdict, with no per-object cryptography in Python.
+
+``class_objectProcessor.processmsg`` (``src/class_objectProcessor.py:435-747``) walks a decrypted msg's
+fields, checks its signature, and hashes the sender's keys into the ripe and the address.  Behind the
+decryption that is one call on the device (:func:`open_msgs`, ``bmpow_rx_msgs``, ``include/bmpow_rx.h``): the
+walk, the signed data, both digests, the curve equation, the ripe, the address and ``sigHash`` give one
+record per msg whose status names the first line of ``processmsg`` that returns; :func:`process_msgs` puts
+:func:`ecies.process_msgs` in front of it.
 
 ``class_objectProcessor.processbroadcast`` (``src/class_objectProcessor.py:749-973``) and
 ``protocol.decryptAndCheckPubkeyPayload`` (``src/protocol.py:401-518``) decrypt an object with a key derived
@@ -8,12 +15,35 @@ device: :func:`addresses.address_keys`, :func:`ecies.decrypt_batch`, :func:`sign
 :func:`addresses.derive_batch`; what stays on the host is slicing and comparing bytes.  No CPU fallback.
 """
 import collections
+import ctypes
 import hashlib
+import struct
 
-from . import addresses, ecies, signatures
+import numpy as np
+
+from . import _lib, addresses, ecies, signatures
 from .ecies import _varint
 
 Broadcast = collections.namedtuple('Broadcast', signatures.BroadcastParts._fields + ('fromAddress', 'ripe', 'sigHash'))
+
+# ``processmsg``'s returning lines as ``bmpow_rx_msgs`` names them (BMPOW_RX_*, include/bmpow_rx.h)
+OK, MSG_VERSION, NOT_MINE, SENDER_VERSION_0, SENDER_VERSION_HIGH = 0, 1, 2, 3, 4
+TOO_SHORT, SENDER_STREAM_0, WRONG_TO_RIPE, VARINT, BAD_SIGNATURE = 5, 6, 7, 8, 9
+STATUS_LINES = {OK: None, MSG_VERSION: 444, NOT_MINE: 478, SENDER_VERSION_0: 492, SENDER_VERSION_HIGH: 496,
+                TOO_SHORT: 500, SENDER_STREAM_0: 506, WRONG_TO_RIPE: 531, VARINT: 'varint', BAD_SIGNATURE: 566}
+
+MSG_REC = np.dtype([('sender_version', np.uint64), ('sender_stream', np.uint64), ('ntpb', np.uint64),
+                    ('extra', np.uint64), ('encoding', np.uint64), ('claimed_stream', np.uint64),
+                    ('end_of_pubkey', np.uint32), ('msg_off', np.uint32), ('msg_len', np.uint32),
+                    ('ack_off', np.uint32), ('ack_len', np.uint32), ('sig_off', np.uint32), ('sig_len', np.uint32),
+                    ('bottom', np.uint32), ('status', np.int32), ('ripe', np.uint8, 20), ('sig_hash', np.uint8, 32),
+                    ('addr_len', np.uint8), ('addr', 'S63'), ('behaviour', np.uint8, 4), ('digest', np.uint8),
+                    ('prefix_len', np.uint8), ('reserved', np.uint8, 2)])
+assert MSG_REC.itemsize == ctypes.sizeof(_lib.BmpowRxMsgRec) == 208
+
+Msg = collections.namedtuple('Msg', [
+    'toRipe', 'senderVersion', 'senderStream', 'behaviour', 'nonceTrialsPerByte', 'extraBytes', 'encoding', 'message',
+    'ackData', 'signature', 'digest', 'pubkeyData', 'fromAddress', 'ripe', 'sigHash'])
 
 
 def _decrypt_grouped(payloads, keys):
@@ -140,3 +170,152 @@ def identify(parts, versions, streams):
     parts = list(parts)
     ident = addresses.derive_batch([p[2] for p in parts], [_encryption_key(p[0], p[2]) for p in parts], versions, streams)
     return [(ident.address(i), ident.ripe[i].tobytes()) for i in range(len(parts))]
+
+
+class OpenedMsgs(object):
+    """A batch's records (``bmpow_rx_msg_rec``) beside the plaintexts they index.  The columns ``status``,
+    ``digest``, ``senderVersion``, ``senderStream``, ``encoding``, ``nonceTrialsPerByte``, ``extraBytes``,
+    ``claimedStream`` and ``behaviour`` are numpy arrays; the accessors slice row ``i``'s plaintext.  The
+    walked fields of a row are filled as far as ``processmsg`` gets before it returns; ``ripe``,
+    ``fromAddress`` and ``sigHash`` belong to rows whose status is ``OK``."""
+
+    def __init__(self, recs, plaintexts):
+        self.recs, self.plaintexts = recs, plaintexts
+        self.status, self.digest = recs['status'], recs['digest']
+        self.senderVersion, self.senderStream = recs['sender_version'], recs['sender_stream']
+        self.encoding, self.behaviour = recs['encoding'], recs['behaviour']
+        self.nonceTrialsPerByte, self.extraBytes = recs['ntpb'], recs['extra']
+        self.claimedStream = recs['claimed_stream']
+
+    def __len__(self):
+        return len(self.recs)
+
+    def _cut(self, i, off, length):
+        r = self.recs[i]
+        return self.plaintexts[i][int(r[off]):int(r[off]) + int(r[length])]
+
+    def message(self, i):
+        return self._cut(i, 'msg_off', 'msg_len')
+
+    def ackData(self, i):
+        return self._cut(i, 'ack_off', 'ack_len')
+
+    def signature(self, i):
+        return self._cut(i, 'sig_off', 'sig_len')
+
+    def pubkeyData(self, i):
+        """``decryptedData[:endOfThePublicKeyPosition]``: what ``:595-601`` stores in the pubkeys table."""
+        return self.plaintexts[i][:int(self.recs[i]['end_of_pubkey'])]
+
+    def fromAddress(self, i):
+        r = self.recs[i]
+        return 'BM-' + bytes(r['addr'])[:int(r['addr_len'])].decode('ascii')
+
+    def ripe(self, i):
+        return self.recs[i]['ripe'].tobytes()
+
+    def sigHash(self, i):
+        return self.recs[i]['sig_hash'].tobytes()
+
+    def accepted(self):
+        """The rows ``processmsg`` would go on with at ``:582``."""
+        return [int(i) for i in np.flatnonzero(self.status == OK)]
+
+
+def _msg_inputs(objects, plaintexts, to_ripes):
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    plains = [p if type(p) is bytes else bytes(p) for p in plaintexts]
+    ripes = [r if type(r) is bytes else bytes(r) for r in to_ripes]
+    if not (len(objs) == len(plains) == len(ripes)):
+        raise ValueError('one plaintext and one toRipe per object')
+    if any(len(r) != 20 for r in ripes):
+        raise ValueError('a toRipe is 20 bytes')
+    return objs, plains, ripes
+
+
+def open_msgs(objects, plaintexts, to_ripes):
+    """``processmsg`` from ``:441`` to ``:591`` for decrypted msgs, in one call on the device
+    (``bmpow_rx_msgs``): per (object, plaintext, ripe of the key that decrypted it) the field walk, the
+    signature check over ``data[8:20] + varint(1) + varint(stream) + plaintext[:bottomOfAckData]``, the
+    sender's ripe and address and ``sigHash``, as an :class:`OpenedMsgs`.  ``status`` is the first line
+    that returns (``STATUS_LINES``)."""
+    objs, plains, ripes = _msg_inputs(objects, plaintexts, to_ripes)
+    n = len(objs)
+    recs = np.zeros(n, dtype=MSG_REC)
+    if n == 0:
+        return OpenedMsgs(recs, plains)
+    lib = _lib.get()
+    op = (ctypes.c_char_p * n)(*objs)
+    pp = (ctypes.c_char_p * n)(*plains)
+    ol = np.fromiter(map(len, objs), dtype=np.uint64, count=n)
+    pl = np.fromiter(map(len, plains), dtype=np.uint64, count=n)
+    _lib.check(lib, lib.bmpow_rx_msgs(n, ctypes.cast(op, ctypes.c_void_p), ol.ctypes.data_as(signatures._P64),
+                                      ctypes.cast(pp, ctypes.c_void_p), pl.ctypes.data_as(signatures._P64),
+                                      b''.join(ripes), recs.ctypes.data), 'bmpow_rx_msgs')
+    return OpenedMsgs(recs, plains)
+
+
+def walk_msg(obj, plaintext, to_ripe):
+    """The walk alone for one msg, on the host by the code the kernel is built from
+    (``bmpow_rx_walk_msg``): ``(record, verifiable)`` -- a one-row :class:`OpenedMsgs` whose status is the
+    walk's (``OK`` where it reaches ``:566``; no verdict, ripe, address or ``sigHash``), and whether the
+    signature is canonical DER with r and s in range and the key's coordinates are below p."""
+    objs, plains, ripes = _msg_inputs([obj], [plaintext], [to_ripe])
+    lib = _lib.host()
+    rec = _lib.BmpowRxMsgRec()
+    rc = _lib.check(lib, lib.bmpow_rx_walk_msg(objs[0], len(objs[0]), plains[0], len(plains[0]), ripes[0],
+                                                ctypes.byref(rec)), 'bmpow_rx_walk_msg')
+    return OpenedMsgs(np.frombuffer(bytes(rec), dtype=MSG_REC).copy(), plains), rc == 1
+
+
+def process_msgs(objects, keys_by_ripe):
+    """``processmsg`` for a batch of msg objects: :func:`ecies.process_msgs` (the decryption loop,
+    ``:459-483``), then :func:`open_msgs`.  Per object None, or a :class:`Msg` where the reference reaches
+    ``:582``.  ``keys_by_ripe`` maps the ripe of each of the user's addresses to its private encryption key.
+
+    Not done here: the recipient's own higher proof-of-work demand (``:615-629``, needs the config and the
+    address book), black and white lists, ``MsgDecode``; see :func:`ack_has_valid_header` for ``:725``."""
+    objs = [bytes(o) for o in objects]
+    opened = ecies.process_msgs(objs, keys_by_ripe)
+    live = [i for i, r in enumerate(opened) if r is not None]
+    out = [None] * len(objs)
+    if not live:
+        return out
+    res = open_msgs([objs[i] for i in live], [opened[i][1] for i in live], [opened[i][0] for i in live])
+    for j in res.accepted():
+        r = res.recs[j]
+        out[live[j]] = Msg(opened[live[j]][0], int(r['sender_version']), int(r['sender_stream']), r['behaviour'].tobytes(),
+                           int(r['ntpb']), int(r['extra']), int(r['encoding']), res.message(j), res.ackData(j),
+                           res.signature(j), int(r['digest']), res.pubkeyData(j), res.fromAddress(j), res.ripe(j),
+                           res.sigHash(j))
+    return out
+
+
+def ack_has_valid_header(ackData):
+    """``objectProcessor.ackDataHasAValidHeader`` (``src/class_objectProcessor.py:1020-1054``), on the host:
+    whether a msg's ackData is one well-formed ``object`` packet, which is what ``:725-731`` asks before the
+    acknowledgement is sent on."""
+    ackData = bytes(ackData)
+    if len(ackData) < 24:
+        return False
+    magic, command, length, checksum = struct.unpack('!L12sL4s', ackData[:24])
+    if magic != 0xE9BEB4D9:
+        return False
+    payload = ackData[24:]
+    if len(payload) != length or length > 1600100:
+        return False
+    if checksum != hashlib.sha512(payload).digest()[:4]:
+        return False
+    return command.rstrip(b'\x00') == b'object'
+
+
+def stats():
+    """The library's msg-processing counters (``bmpow_rx_stats``) as a dict."""
+    lib = _lib.get()
+    st = _lib.BmpowRxStats()
+    _lib.check(lib, lib.bmpow_rx_get_stats(ctypes.byref(st)), 'bmpow_rx_get_stats')
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def reset_stats():
+    _lib.get().bmpow_rx_reset_stats()

@@ -317,6 +317,32 @@ RX_SIGNATURES = [
     ('bmpow_rx_reset_stats', None, []),
 ]
 
+
+
+class BmpowRxObjRec(ctypes.Structure):
+    """``bmpow_rx_obj_rec`` (include/bmpow_rx.h): one processed broadcast or pubkey, 216 bytes."""
+    _fields_ = [('object_version', ctypes.c_uint64), ('object_stream', ctypes.c_uint64),
+                ('sender_version', ctypes.c_uint64), ('sender_stream', ctypes.c_uint64), ('ntpb', ctypes.c_uint64),
+                ('extra', ctypes.c_uint64), ('encoding', ctypes.c_uint64), ('payload_off', ctypes.c_uint32),
+                ('tag_off', ctypes.c_uint32), ('end_of_pubkey', ctypes.c_uint32), ('msg_off', ctypes.c_uint32),
+                ('msg_len', ctypes.c_uint32), ('sig_off', ctypes.c_uint32), ('sig_len', ctypes.c_uint32),
+                ('bottom', ctypes.c_uint32), ('status', ctypes.c_int32), ('ripe', ctypes.c_uint8 * 20),
+                ('sig_hash', ctypes.c_uint8 * 32), ('addr_len', ctypes.c_uint8), ('addr', ctypes.c_char * 63),
+                ('behaviour', ctypes.c_uint8 * 4), ('digest', ctypes.c_uint8), ('prefix_len', ctypes.c_uint8),
+                ('kind', ctypes.c_uint8), ('keys_hashed', ctypes.c_uint8)]
+
+
+# the broadcast and pubkey half of include/bmpow_rx.h; its counters are a second bmpow_rx_stats
+RXOBJ_SIGNATURES = [
+    ('bmpow_rx_objects', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p, _p64, ctypes.c_void_p, _p64, ctypes.c_char_p, ctypes.c_void_p]),
+    ('bmpow_rx_walk_object', ctypes.c_int,
+     [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+      ctypes.POINTER(BmpowRxObjRec)]),
+    ('bmpow_rx_obj_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowRxStats)]),
+    ('bmpow_rx_obj_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -335,7 +361,7 @@ def load(path=None):
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
-                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES):
+                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -2,7 +2,9 @@
 // of processmsg (src/class_objectProcessor.py:441-452, :488-561), the strict DER parse of the signature,
 // the prefix of signedData (:562-564) and the packing of signedData into padded SHA blocks, written once
 // for the device (bmpow_rx.hip), for the host-only entry point (bmpow_rx_walk_msg, bmpow_host_rx.hip) and
-// for the stand-alone test program (tests/native/rx_sim.cpp builds this header with g++).
+// for the stand-alone test program (tests/native/rx_sim.cpp builds this header with g++).  Behind the msgs'
+// part: the walks of processbroadcast, decryptAndCheckPubkeyPayload and processpubkey and their prefix of up
+// to 62 bytes (bmpow_rxobj.hip, bmpow_rx_walk_object in bmpow_host_rxobj.hip, tests/native/rxobj_sim.cpp).
 //
 // Positions are 64-bit and saturate: a length varint may be 2^64 - 1, and a slice that starts or ends past
 // the plaintext is cut at its end as Python cuts it.  Bytes are read one at a time through a plain pointer
@@ -232,24 +234,25 @@ RX_HD uint32_t signed_blocks(uint32_t prefix_len, uint32_t bottom) {  // ceil((l
 // what the host reserves before the walk has run: no prefix is longer than 22 bytes, bottom <= len
 RX_HD uint32_t signed_blocks_bound(uint64_t plain_len) { return (uint32_t)((22 + plain_len + 9 + 63) / 64); }
 
-RX_HD uint32_t word_at(const uint32_t (&pre)[6], uint32_t q) {  // no run-time index: one select per word
+template <int NW>
+RX_HD uint32_t word_at(const uint32_t (&pre)[NW], uint32_t q) {  // no run-time index: one select per word
   uint32_t w = 0;
   RX_UNROLL
-  for (int i = 0; i < 6; ++i) w = q == (uint32_t)i ? pre[i] : w;
+  for (int i = 0; i < NW; ++i) w = q == (uint32_t)i ? pre[i] : w;
   return w;
 }
 
 // Chunk c (16 bytes, four words in memory order) of the padded signed data
-//     prefix[:plen] || plaintext[:bottom] || 0x80 || zeros || the bit length as 8 big-endian bytes
-// of nblk 64-byte blocks.  src.load16(k, w) gives bytes [16 k, 16 k + 16) of the plaintext as four words
-// (zero past its storage), src.byte(i) one byte.  A chunk that lies within the plaintext is two aligned
-// 16-byte loads funnelled by the prefix's length; only the chunks at either end go byte by byte.
-template <class Src>
-RX_HD void pack_chunk(uint32_t c, uint32_t nblk, const uint32_t (&pre)[6], uint32_t plen, uint32_t bottom, const Src& src,
-                      uint32_t (&out)[4]) {
+//     prefix[:plen] || source[skip : skip + bottom] || 0x80 || zeros || the bit length as 8 big-endian bytes
+// of nblk 64-byte blocks; the prefix is NW words.  src.load16(k, w) gives bytes [16 k, 16 k + 16) of the
+// source as four words (zero past its storage), src.byte(i) one byte.  A chunk that lies within the source is
+// two aligned 16-byte loads funnelled by (skip - plen) mod 16; only the chunks at either end go byte by byte.
+template <int NW, class Src>
+RX_HD void pack_chunk_n(uint32_t c, uint32_t nblk, const uint32_t (&pre)[NW], uint32_t plen, uint32_t bottom, uint32_t skip,
+                        const Src& src, uint32_t (&out)[4]) {
   const uint64_t q0 = 16ull * c, len = (uint64_t)plen + bottom, total = 64ull * nblk;
   if (q0 >= plen && q0 + 16 <= len) {
-    const uint64_t a = q0 - plen;
+    const uint64_t a = q0 - plen + skip;
     const uint32_t k = (uint32_t)(a >> 4), sh = (uint32_t)a & 15u, ws = sh >> 2, bs = 8 * (sh & 3u);
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t lo[4], hi[4] = {0, 0, 0, 0};
@@ -273,11 +276,254 @@ RX_HD void pack_chunk(uint32_t c, uint32_t nblk, const uint32_t (&pre)[6], uint3
     const uint64_t q = q0 + j;
     uint32_t b = 0;
     if (q < plen) b = (word_at(pre, (uint32_t)q >> 2) >> (8 * ((uint32_t)q & 3))) & 0xffu;
-    else if (q < len) b = src.byte((uint32_t)(q - plen));
+    else if (q < len) b = src.byte((uint32_t)(q - plen) + skip);
     else if (q == len) b = 0x80u;
     else if (q + 8 >= total) b = (uint32_t)(bits >> (8 * (total - 1 - q))) & 0xffu;
     out[j >> 2] |= b << (8 * (j & 3));
   }
 }
+
+// the msgs' instantiation: six words of prefix (14 .. 22 bytes), the plaintext from its first byte
+template <class Src>
+RX_HD void pack_chunk(uint32_t c, uint32_t nblk, const uint32_t (&pre)[6], uint32_t plen, uint32_t bottom, const Src& src,
+                      uint32_t (&out)[4]) {
+  pack_chunk_n<6>(c, nblk, pre, plen, bottom, 0u, src, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Broadcasts and pubkeys (bmpow_rxobj.hip, bmpow_rx_walk_object): processbroadcast
+// (src/class_objectProcessor.py:756-926), decryptAndCheckPubkeyPayload (src/protocol.py:412-518) and
+// processpubkey (:276-408).  rec must be zeroed but for its kind.
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t kObjHeadBytes = 70;    // data[:70]: nonce, time, type, two varints of at most 9 bytes, a tag
+constexpr uint32_t kObjPrefixWords = 16;  // obj[8:payload_off]: at most 62 bytes
+constexpr uint32_t kV2Min = 146;          // :293
+constexpr uint32_t kV3Min = 170;          // :346
+
+struct obj_walk {
+  uint32_t key_off;  // where the two 64-byte keys start in the source
+  uint32_t skip;     // where the signed bytes start in the source (8 for a clear pubkey)
+  bool keys;         // the keys lie whole in the source and go to the identification
+  bool sig;          // the walk got through and there is a signature to check
+};
+
+RX_HD void clipped4(const uint8_t* p, uint64_t len, uint64_t pos, uint8_t (&out)[4]) {
+  RX_UNROLL
+  for (int i = 0; i < 4; ++i) out[i] = pos + i < len ? p[pos + i] : (uint8_t)0;
+}
+
+// The header of a broadcast: :756-769 and the tag of :808.  status is OK where the walk goes on.
+RX_HD void walk_broadcast_header(const uint8_t* head, uint32_t hlen, bmpow_rx_obj_rec& rec) {
+  rec.status = BMPOW_RXO_VARINT;
+  const varint bv = get_varint(head, hlen, 20);
+  if (!bv.ok) return;
+  rec.object_version = bv.v;
+  if (bv.v < 4 || bv.v > 5) {
+    rec.status = BMPOW_RXO_BC_VERSION;
+    return;
+  }
+  const varint st = get_varint(head, hlen, 20 + bv.n);
+  if (!st.ok) return;
+  rec.object_stream = st.v;
+  const uint32_t pos = 20 + bv.n + st.n;  // <= hlen: bv was read there
+  rec.tag_off = pos;
+  rec.payload_off = bv.v == 5 ? (uint32_t)min64(pos + 32, hlen) : pos;
+  rec.prefix_len = (uint8_t)(rec.payload_off - 8);
+  rec.status = BMPOW_RXO_OK;
+}
+
+RX_HD void walk_broadcast(const uint8_t* head, uint32_t hlen, const uint8_t* p, uint64_t len, bmpow_rx_obj_rec& rec,
+                          obj_walk& w) {
+  walk_broadcast_header(head, hlen, rec);
+  if (rec.status != BMPOW_RXO_OK) return;
+  rec.status = BMPOW_RXO_VARINT;
+  const bool v4 = rec.object_version == 4;
+  const varint ver = get_varint(p, len, 0);
+  if (!ver.ok) return;
+  rec.sender_version = ver.v;
+  if (v4 ? (ver.v < 2 || ver.v > 3) : ver.v < 4) {
+    rec.status = BMPOW_RXO_SENDER_VERSION;
+    return;
+  }
+  uint64_t pos = ver.n;
+  const varint stream = get_varint(p, len, pos);
+  if (!stream.ok) return;
+  rec.sender_stream = stream.v;
+  if (stream.v != rec.object_stream) {
+    rec.status = BMPOW_RXO_STREAM_MISMATCH;
+    return;
+  }
+  pos += stream.n;
+  clipped4(p, len, pos, rec.behaviour);
+  pos += 4;
+  w.key_off = (uint32_t)pos;  // at most 22
+  pos += 128;
+  if (ver.v >= 3) {
+    const varint ntpb = get_varint(p, len, pos);
+    if (!ntpb.ok) return;
+    rec.ntpb = ntpb.v;
+    pos += ntpb.n;
+    const varint extra = get_varint(p, len, pos);
+    if (!extra.ok) return;
+    rec.extra = extra.v;
+    pos += extra.n;
+  }
+  rec.end_of_pubkey = (uint32_t)min64(pos, len);
+  // :882 / :893.  Keys cut short by the end of the plaintext hash to another ripe and another tag, and a tag
+  // cut short by the end of the object equals no 32 bytes: those are decided here; whole ones on the device.
+  if (len < (uint64_t)w.key_off + 128 || (!v4 && rec.payload_off - rec.tag_off != 32)) {
+    rec.status = v4 ? BMPOW_RXO_WRONG_RIPE : BMPOW_RXO_WRONG_TAG;
+    return;
+  }
+  w.keys = true;
+  rec.keys_hashed = 1;
+  const varint enc = get_varint(p, len, pos);
+  if (!enc.ok) return;
+  rec.encoding = enc.v;
+  if (enc.v == 0) {
+    rec.status = BMPOW_RXO_ENCODING_0;
+    return;
+  }
+  pos += enc.n;
+  const varint mlen = get_varint(p, len, pos);
+  if (!mlen.ok) return;
+  pos += mlen.n;
+  slice(len, pos, mlen.v, rec.msg_off, rec.msg_len);
+  pos = sat_add(pos, mlen.v);
+  rec.bottom = (uint32_t)min64(pos, len);
+  const varint slen = get_varint(p, len, pos);
+  if (!slen.ok) return;
+  pos = sat_add(pos, slen.n);
+  slice(len, pos, slen.v, rec.sig_off, rec.sig_len);
+  rec.status = BMPOW_RXO_OK;
+  w.sig = true;
+}
+
+// The header of an encrypted pubkey: protocol.py:412-439
+RX_HD void walk_pubkey_v4_header(const uint8_t* head, uint32_t hlen, bmpow_rx_obj_rec& rec) {
+  rec.status = BMPOW_RXO_VARINT;
+  const varint ver = get_varint(head, hlen, 20);
+  if (!ver.ok) return;
+  rec.object_version = ver.v;
+  const varint st = get_varint(head, hlen, 20 + ver.n);
+  if (!st.ok) return;
+  rec.object_stream = st.v;
+  rec.tag_off = (uint32_t)min64(20 + ver.n + st.n, hlen);
+  rec.payload_off = (uint32_t)min64(rec.tag_off + 32, hlen);
+  rec.prefix_len = (uint8_t)(rec.payload_off > 8 ? rec.payload_off - 8 : 0);
+  rec.status = BMPOW_RXO_OK;
+}
+
+RX_HD void walk_pubkey_v4(const uint8_t* head, uint32_t hlen, const uint8_t* p, uint64_t len, bmpow_rx_obj_rec& rec,
+                          obj_walk& w) {
+  walk_pubkey_v4_header(head, hlen, rec);
+  if (rec.status != BMPOW_RXO_OK) return;
+  rec.status = BMPOW_RXO_VARINT;
+  rec.sender_version = rec.object_version;
+  rec.sender_stream = rec.object_stream;
+  clipped4(p, len, 0, rec.behaviour);
+  w.key_off = 4;
+  uint64_t pos = 132;
+  const varint ntpb = get_varint(p, len, pos);
+  if (!ntpb.ok) return;
+  rec.ntpb = ntpb.v;
+  pos += ntpb.n;
+  const varint extra = get_varint(p, len, pos);
+  if (!extra.ok) return;
+  rec.extra = extra.v;
+  pos += extra.n;
+  rec.end_of_pubkey = rec.bottom = (uint32_t)min64(pos, len);
+  const varint slen = get_varint(p, len, pos);
+  if (!slen.ok) return;
+  pos += slen.n;
+  slice(len, pos, slen.v, rec.sig_off, rec.sig_len);
+  if (len < 132) {  // a key cut short is no key: verify says False (protocol.py:484)
+    rec.status = BMPOW_RXO_BAD_SIGNATURE;
+    return;
+  }
+  w.keys = w.sig = true;
+  rec.keys_hashed = 1;
+  rec.status = BMPOW_RXO_OK;
+}
+
+// A clear pubkey, p the object itself: :276-308 (version 2) and :345-368 (version 3)
+RX_HD void walk_pubkey(const uint8_t* p, uint64_t len, bmpow_rx_obj_rec& rec, obj_walk& w) {
+  rec.status = BMPOW_RXO_VARINT;
+  const varint ver = get_varint(p, len, 20);
+  if (!ver.ok) return;
+  const varint st = get_varint(p, len, 20 + ver.n);
+  if (!st.ok) return;
+  rec.object_version = rec.sender_version = ver.v;
+  rec.object_stream = rec.sender_stream = st.v;
+  uint64_t pos = 20 + ver.n + st.n;
+  rec.payload_off = (uint32_t)min64(pos, len);
+  if (ver.v < 2 || ver.v > 3) {
+    rec.status = ver.v == 0 ? BMPOW_RXO_ADDRESS_VERSION_0 : ver.v == 4 ? BMPOW_RXO_NEEDS_DECRYPTION : BMPOW_RXO_ADDRESS_VERSION;
+    return;
+  }
+  if (len < (ver.v == 2 ? kV2Min : kV3Min)) {
+    rec.status = BMPOW_RXO_TOO_SHORT;
+    return;
+  }
+  clipped4(p, len, pos, rec.behaviour);
+  pos += 4;
+  w.key_off = (uint32_t)pos;  // at most 42
+  if (ver.v == 2) {
+    if (len - (pos + 64) < 64) {  // pos + 64 <= 106 < 146 <= len
+      rec.status = BMPOW_RXO_KEY_SHORT;
+      return;
+    }
+    rec.end_of_pubkey = (uint32_t)pos + 128;
+    w.keys = true;
+    rec.keys_hashed = 1;
+    rec.status = BMPOW_RXO_OK;
+    return;
+  }
+  pos += 128;  // at most 170 <= len
+  const varint ntpb = get_varint(p, len, pos);
+  if (!ntpb.ok) return;
+  rec.ntpb = ntpb.v;
+  pos += ntpb.n;
+  const varint extra = get_varint(p, len, pos);
+  if (!extra.ok) return;
+  rec.extra = extra.v;
+  pos += extra.n;  // a varint that was read lies inside: pos <= len
+  rec.end_of_pubkey = (uint32_t)pos;
+  rec.bottom = (uint32_t)pos - 8;
+  w.skip = 8;
+  const varint slen = get_varint(p, len, pos);
+  if (!slen.ok) return;
+  pos += slen.n;
+  slice(len, pos, slen.v, rec.sig_off, rec.sig_len);
+  w.keys = w.sig = true;
+  rec.keys_hashed = 1;
+  rec.status = BMPOW_RXO_OK;
+}
+
+// one row of any kind; kind is one of BMPOW_RXO_KIND_*
+RX_HD void walk_object(uint32_t kind, const uint8_t* head, uint32_t hlen, const uint8_t* p, uint64_t len,
+                       bmpow_rx_obj_rec& rec, obj_walk& w) {
+  w.key_off = w.skip = 0;
+  w.keys = w.sig = false;
+  rec.kind = (uint8_t)kind;
+  if (kind == BMPOW_RXO_KIND_BROADCAST) walk_broadcast(head, hlen, p, len, rec, w);
+  else if (kind == BMPOW_RXO_KIND_PUBKEY_V4) walk_pubkey_v4(head, hlen, p, len, rec, w);
+  else walk_pubkey(p, len, rec, w);
+}
+
+// obj[8:payload_off] as 64 bytes in memory order, zero behind its prefix_len bytes; head holds hlen >=
+// payload_off bytes
+RX_HD void put_prefix_obj(const uint8_t* head, uint32_t payload_off, uint32_t (&pre)[kObjPrefixWords]) {
+  RX_UNROLL
+  for (int i = 0; i < (int)kObjPrefixWords; ++i) pre[i] = 0;
+  RX_UNROLL
+  for (int i = 0; i < 62; ++i) {
+    const uint32_t b = 8u + (uint32_t)i < payload_off ? head[8 + i] : 0u;
+    pre[i >> 2] |= b << (8 * (i & 3));
+  }
+}
+
+// what the host reserves for a row before the walk has run: no prefix is longer than 62 bytes
+RX_HD uint32_t signed_blocks_bound_obj(uint64_t source_len) { return (uint32_t)((62 + source_len + 9 + 63) / 64); }
 
 }  // namespace rxf

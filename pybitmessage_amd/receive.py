@@ -13,6 +13,11 @@ from an address, check its signature, hash the sender's keys into the ripe and c
 made from it) with what the object was encrypted for.  Here each of those steps is one batched call on the
 device: :func:`addresses.address_keys`, :func:`ecies.decrypt_batch`, :func:`signatures.verify_batch`,
 :func:`addresses.derive_batch`; what stays on the host is slicing and comparing bytes.  No CPU fallback.
+
+The same two functions, and ``processpubkey`` (``src/class_objectProcessor.py:270-433``) for clear v2 / v3
+pubkeys, also run behind their decryption as one call on the device (:func:`open_objects`,
+``bmpow_rx_objects``), as msgs do: :func:`open_broadcasts` and :func:`open_pubkeys` give one record per object
+whose status names the reference line that returns, so "not for me" and "forged" can be told apart.
 """
 import collections
 import ctypes
@@ -307,6 +312,260 @@ def ack_has_valid_header(ackData):
     if checksum != hashlib.sha512(payload).digest()[:4]:
         return False
     return command.rstrip(b'\x00') == b'object'
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Broadcasts and pubkeys in one device call (``bmpow_rx_objects``, include/bmpow_rx.h)
+# ---------------------------------------------------------------------------------------------------------
+KIND_BROADCAST, KIND_PUBKEY_V4, KIND_PUBKEY = 0, 1, 2
+(OBJ_OK, OBJ_VARINT, OBJ_BC_VERSION, OBJ_SENDER_VERSION, OBJ_STREAM_MISMATCH, OBJ_WRONG_RIPE, OBJ_WRONG_TAG,
+ OBJ_ENCODING_0, OBJ_BAD_SIGNATURE, OBJ_ADDRESS_VERSION_0, OBJ_ADDRESS_VERSION, OBJ_NEEDS_DECRYPTION, OBJ_TOO_SHORT,
+ OBJ_KEY_SHORT, OBJ_NOT_SUBSCRIBED, OBJ_NOT_DECRYPTED, OBJ_NOT_NEEDED, OBJ_ADDRESS_MISMATCH,
+ OBJ_V4_TOO_SHORT) = range(19)
+# per kind: status -> the reference lines that return with it (``src/class_objectProcessor.py``; for
+# ``KIND_PUBKEY_V4`` ``src/protocol.py`` but for 411 and 417, which are ``processpubkey``'s)
+OBJ_STATUS_LINES = {
+    KIND_BROADCAST: {OBJ_OK: (None,), OBJ_VARINT: ('varint',), OBJ_BC_VERSION: (760,), OBJ_SENDER_VERSION: (830, 838),
+                     OBJ_STREAM_MISMATCH: (848,), OBJ_WRONG_RIPE: (882,), OBJ_WRONG_TAG: (893,), OBJ_ENCODING_0: (901,),
+                     OBJ_BAD_SIGNATURE: (916,), OBJ_NOT_SUBSCRIBED: (801, 810), OBJ_NOT_DECRYPTED: (820,)},
+    KIND_PUBKEY_V4: {OBJ_OK: (None,), OBJ_VARINT: ('varint',), OBJ_BAD_SIGNATURE: (484,), OBJ_WRONG_RIPE: (497,),
+                     OBJ_NOT_DECRYPTED: (457,), OBJ_NOT_NEEDED: (417, 442), OBJ_ADDRESS_MISMATCH: (423, 428),
+                     OBJ_V4_TOO_SHORT: (411,)},
+    KIND_PUBKEY: {OBJ_OK: (None,), OBJ_VARINT: ('varint',), OBJ_ADDRESS_VERSION_0: (283,), OBJ_ADDRESS_VERSION: (287,),
+                  OBJ_NEEDS_DECRYPTION: (410,), OBJ_TOO_SHORT: (293, 346), OBJ_KEY_SHORT: (304,),
+                  OBJ_BAD_SIGNATURE: (374,)},
+}
+
+OBJ_REC = np.dtype([('object_version', np.uint64), ('object_stream', np.uint64), ('sender_version', np.uint64),
+                    ('sender_stream', np.uint64), ('ntpb', np.uint64), ('extra', np.uint64), ('encoding', np.uint64),
+                    ('payload_off', np.uint32), ('tag_off', np.uint32), ('end_of_pubkey', np.uint32),
+                    ('msg_off', np.uint32), ('msg_len', np.uint32), ('sig_off', np.uint32), ('sig_len', np.uint32),
+                    ('bottom', np.uint32), ('status', np.int32), ('ripe', np.uint8, 20), ('sig_hash', np.uint8, 32),
+                    ('addr_len', np.uint8), ('addr', 'S63'), ('behaviour', np.uint8, 4), ('digest', np.uint8),
+                    ('prefix_len', np.uint8), ('kind', np.uint8), ('keys_hashed', np.uint8)])
+assert OBJ_REC.itemsize == ctypes.sizeof(_lib.BmpowRxObjRec) == 216
+
+
+class OpenedObjects(object):
+    """A batch's records (``bmpow_rx_obj_rec``) beside the objects and plaintexts they index.  ``status``,
+    ``kind``, ``digest``, ``objectVersion``, ``objectStream``, ``senderVersion``, ``senderStream``, ``encoding``,
+    ``nonceTrialsPerByte``, ``extraBytes`` and ``behaviour`` are numpy columns; the accessors slice row ``i``'s
+    plaintext (the object itself for a clear pubkey).  Walked fields are filled as far as the reference gets
+    before it returns; ``ripe``, ``fromAddress`` and ``sigHash`` belong to rows whose status is ``OBJ_OK``."""
+
+    def __init__(self, recs, objects, plaintexts):
+        self.recs, self.objects, self.plaintexts = recs, objects, plaintexts
+        self.status, self.kind, self.digest = recs['status'], recs['kind'], recs['digest']
+        self.objectVersion, self.objectStream = recs['object_version'], recs['object_stream']
+        self.senderVersion, self.senderStream = recs['sender_version'], recs['sender_stream']
+        self.encoding, self.behaviour = recs['encoding'], recs['behaviour']
+        self.nonceTrialsPerByte, self.extraBytes = recs['ntpb'], recs['extra']
+
+    def __len__(self):
+        return len(self.recs)
+
+    def _source(self, i):
+        return self.objects[i] if self.recs[i]['kind'] == KIND_PUBKEY else self.plaintexts[i]
+
+    def _cut(self, i, off, length):
+        r = self.recs[i]
+        return self._source(i)[int(r[off]):int(r[off]) + int(r[length])]
+
+    def message(self, i):
+        return self._cut(i, 'msg_off', 'msg_len')
+
+    def signature(self, i):
+        return self._cut(i, 'sig_off', 'sig_len')
+
+    def signedData(self, i):
+        r = self.recs[i]
+        skip = 8 if r['kind'] == KIND_PUBKEY else 0
+        return self.objects[i][8:8 + int(r['prefix_len'])] + self._source(i)[skip:skip + int(r['bottom'])]
+
+    def pubkeyData(self, i):
+        """A broadcast's ``decryptedData[:endOfPubkeyPosition]``: what ``:930-935`` stores."""
+        return self.plaintexts[i][:int(self.recs[i]['end_of_pubkey'])]
+
+    def storedData(self, i):
+        """What a pubkey's row of the pubkeys table holds: ``data[20:readPosition]`` of a clear pubkey
+        (``:310``, ``:364``), ``data[20:tagOffset] + decryptedData[:endOfKeys]`` of an encrypted one
+        (``src/protocol.py:421``, ``:477``)."""
+        r = self.recs[i]
+        if r['kind'] == KIND_PUBKEY:
+            return self.objects[i][20:int(r['end_of_pubkey'])]
+        return self.objects[i][20:int(r['tag_off'])] + self.plaintexts[i][:int(r['end_of_pubkey'])]
+
+    def fromAddress(self, i):
+        r = self.recs[i]
+        return 'BM-' + bytes(r['addr'])[:int(r['addr_len'])].decode('ascii')
+
+    def ripe(self, i):
+        return self.recs[i]['ripe'].tobytes()
+
+    def sigHash(self, i):
+        return self.recs[i]['sig_hash'].tobytes()
+
+    def accepted(self):
+        """The rows the reference would go on to store."""
+        return [int(i) for i in np.flatnonzero(self.status == OBJ_OK)]
+
+
+def _obj_inputs(kinds, objects, plaintexts, expects):
+    kinds = [int(k) for k in kinds]
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    plains = [b'' if p is None else p if type(p) is bytes else bytes(p) for p in plaintexts]
+    slots = [bytes(e or b'') for e in expects]
+    if not (len(kinds) == len(objs) == len(plains) == len(slots)):
+        raise ValueError('one kind, one plaintext and one expected value per object')
+    if any(k not in (KIND_BROADCAST, KIND_PUBKEY_V4, KIND_PUBKEY) for k in kinds):
+        raise ValueError('a kind is KIND_BROADCAST, KIND_PUBKEY_V4 or KIND_PUBKEY')
+    if any(len(e) > 32 for e in slots):
+        raise ValueError('an expected ripe is 20 bytes (at most the 32 of its slot)')
+    return kinds, objs, plains, [e.ljust(32, b'\x00') for e in slots]
+
+
+def open_objects(kinds, objects, plaintexts, expects):
+    """The raw call (``bmpow_rx_objects``): rows of any kinds in one pass over the device, as an
+    :class:`OpenedObjects`.  Per row the kind (``KIND_*``), the object, its decrypted payload (ignored, and may
+    be None, for ``KIND_PUBKEY``) and the expected ripe: of the subscription key that opened a v4 broadcast, of
+    the address an encrypted pubkey was asked for; unused (None) otherwise."""
+    kinds, objs, plains, slots = _obj_inputs(kinds, objects, plaintexts, expects)
+    n = len(objs)
+    recs = np.zeros(n, dtype=OBJ_REC)
+    if n == 0:
+        return OpenedObjects(recs, objs, plains)
+    lib = _lib.get()
+    op = (ctypes.c_char_p * n)(*objs)
+    pp = (ctypes.c_char_p * n)(*plains)
+    ol = np.fromiter(map(len, objs), dtype=np.uint64, count=n)
+    pl = np.fromiter(map(len, plains), dtype=np.uint64, count=n)
+    _lib.check(lib, lib.bmpow_rx_objects(n, bytes(kinds), ctypes.cast(op, ctypes.c_void_p), ol.ctypes.data_as(signatures._P64),
+                                         ctypes.cast(pp, ctypes.c_void_p), pl.ctypes.data_as(signatures._P64),
+                                         b''.join(slots), recs.ctypes.data), 'bmpow_rx_objects')
+    return OpenedObjects(recs, objs, plains)
+
+
+def _walk_objects(kind, objs, plains=None):
+    """``bmpow_rx_walk_object`` per object into one record array (host only); ``plains`` None: for an
+    encrypted kind the headers alone."""
+    lib = _lib.host()
+    recs = np.zeros(len(objs), dtype=OBJ_REC)
+    view = (_lib.BmpowRxObjRec * len(objs)).from_buffer(recs) if len(objs) else ()
+    verifiable = []
+    for i, o in enumerate(objs):
+        p = None if plains is None else plains[i]
+        verifiable.append(_lib.check(lib, lib.bmpow_rx_walk_object(kind, o, len(o), p, 0 if p is None else len(p), None,
+                                                                    ctypes.byref(view[i])), 'bmpow_rx_walk_object') == 1)
+    return recs, verifiable
+
+
+def walk_object(kind, obj, plaintext=None):
+    """The walk alone for one row, on the host by the code the kernel is built from
+    (``bmpow_rx_walk_object``): ``(record, verifiable)`` -- a one-row :class:`OpenedObjects` and whether the
+    signature and key would go to the curve kernels as they stand.  With ``plaintext`` None for an encrypted
+    kind only the header is walked.  A row whose ``keys_hashed`` is set still awaits the ripe / tag
+    comparison, which for a broadcast comes before the status the record shows."""
+    kinds, objs, plains, _ = _obj_inputs([kind], [obj], [plaintext], [None])
+    recs, verifiable = _walk_objects(kinds[0], objs, None if plaintext is None and kinds[0] != KIND_PUBKEY else plains)
+    return OpenedObjects(recs, objs, plains), verifiable[0]
+
+
+def open_broadcasts(objects, subscriptions):
+    """``processbroadcast`` from ``:756`` to ``:926`` for a batch, with a status for every object
+    (``OBJ_STATUS_LINES[KIND_BROADCAST]``): the headers on the host (``bmpow_rx_walk_object``), the tag lookup
+    for v5 and the trial decryption for v4 as :func:`process_broadcasts` groups them, then one
+    :func:`open_objects` over everything that decrypted.  ``subscriptions`` as for :func:`process_broadcasts`."""
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    n = len(objs)
+    by_ripe, by_tag = collections.OrderedDict(), {}
+    for status, version, _stream, _ripe, lookup, priv in addresses.address_keys(subscriptions):
+        if status == 'success':
+            (by_ripe if version <= 3 else by_tag).setdefault(lookup, priv)
+    recs, _ = _walk_objects(KIND_BROADCAST, objs)
+    plain, expect = [None] * n, [None] * n
+    heads = [i for i in range(n) if recs['status'][i] == OBJ_OK]
+    tags = {i: objs[i][int(recs['tag_off'][i]):int(recs['payload_off'][i])] for i in heads if recs['object_version'][i] == 5}
+    for i, tag in tags.items():
+        recs['status'][i] = OBJ_NOT_DECRYPTED if tag in by_tag else OBJ_NOT_SUBSCRIBED
+    v5 = [i for i, tag in tags.items() if tag in by_tag]
+    for i, p in zip(v5, _decrypt_grouped([objs[i][int(recs['payload_off'][i]):] for i in v5], [by_tag[tags[i]] for i in v5])):
+        plain[i] = p
+    v4 = [i for i in heads if recs['object_version'][i] == 4]
+    for i in v4:
+        recs['status'][i] = OBJ_NOT_SUBSCRIBED
+    if v4 and by_ripe:
+        ripes = list(by_ripe)
+        opened = ecies.decrypt_batch([objs[i][int(recs['payload_off'][i]):] for i in v4], [by_ripe[r] for r in ripes])
+        for i, r in zip(v4, opened):
+            if r is not None:
+                expect[i], plain[i] = ripes[r[0]], r[1]
+    live = [i for i in range(n) if plain[i] is not None]
+    if live:
+        res = open_objects([KIND_BROADCAST] * len(live), [objs[i] for i in live], [plain[i] for i in live],
+                           [expect[i] for i in live])
+        recs[live] = res.recs
+    return OpenedObjects(recs, objs, [p or b'' for p in plain])
+
+
+def open_pubkeys(objects, needed):
+    """``processpubkey`` (``:276-428``) for a batch, with a status for every object: clear v2 / v3 pubkeys and
+    encrypted v4 ones in the same device call.  ``needed`` is ``state.neededPubkeys``: tag -> address string
+    (or a tuple that starts with it) of the v4 addresses whose pubkey is awaited.  A v4 pubkey goes through
+    ``:411`` (``OBJ_V4_TOO_SHORT``), ``:417`` (``OBJ_NOT_NEEDED``), the address's version and stream against
+    the object's (``OBJ_ADDRESS_MISMATCH``), the decryption under the address's key (``OBJ_NOT_DECRYPTED``)
+    and then the device, as ``decryptAndCheckPubkeyPayload`` does."""
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    n = len(objs)
+    recs, _ = _walk_objects(KIND_PUBKEY, objs)
+    v4 = [i for i in range(n) if recs['status'][i] == OBJ_NEEDS_DECRYPTION]
+    if v4:
+        recs[v4] = _walk_objects(KIND_PUBKEY_V4, [objs[i] for i in v4])[0]
+    asked = {}
+    for i in v4:
+        tag = objs[i][int(recs['tag_off'][i]):int(recs['payload_off'][i])]
+        if len(objs[i]) < 350:
+            recs['status'][i] = OBJ_V4_TOO_SHORT
+        elif tag not in needed:
+            recs['status'][i] = OBJ_NOT_NEEDED
+        else:
+            entry = needed[tag]
+            asked[i] = (tag, entry if isinstance(entry, str) else entry[0])
+    plain, expect = [None] * n, [None] * n
+    want = sorted(asked)
+    keys = dict(zip(want, addresses.address_keys([asked[i][1] for i in want])))
+    for i in list(want):
+        status, version, stream, _ripe, lookup, _priv = keys[i]
+        if status != 'success' or version != recs['object_version'][i] or stream != recs['object_stream'][i]:
+            recs['status'][i] = OBJ_ADDRESS_MISMATCH
+        elif lookup != asked[i][0]:  # the entry is another address's: protocol.py:442-454
+            recs['status'][i] = OBJ_NOT_NEEDED
+        else:
+            continue
+        want.remove(i)
+    for i, p in zip(want, _decrypt_grouped([objs[i][int(recs['payload_off'][i]):] for i in want], [keys[i][5] for i in want])):
+        if p is None:
+            recs['status'][i] = OBJ_NOT_DECRYPTED
+        else:
+            plain[i], expect[i] = p, keys[i][3]
+    clear = [i for i in range(n) if recs['kind'][i] == KIND_PUBKEY and recs['status'][i] == OBJ_OK]
+    live = sorted(clear + [i for i in want if plain[i] is not None])
+    if live:
+        res = open_objects([int(recs['kind'][i]) for i in live], [objs[i] for i in live], [plain[i] for i in live],
+                           [expect[i] for i in live])
+        recs[live] = res.recs
+    return OpenedObjects(recs, objs, [p or b'' for p in plain])
+
+
+def obj_stats():
+    """The counters of ``bmpow_rx_objects`` (``bmpow_rx_obj_stats``) as a dict; :func:`stats` stays msgs only."""
+    lib = _lib.get()
+    st = _lib.BmpowRxStats()
+    _lib.check(lib, lib.bmpow_rx_obj_get_stats(ctypes.byref(st)), 'bmpow_rx_obj_get_stats')
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def obj_reset_stats():
+    _lib.get().bmpow_rx_obj_reset_stats()
 
 
 def stats():

@@ -343,6 +343,40 @@ RXOBJ_SIGNATURES = [
     ('bmpow_rx_obj_reset_stats', None, []),
 ]
 
+
+class BmpowTxRec(ctypes.Structure):
+    """``bmpow_tx_rec`` (include/bmpow_tx.h): one built object, 152 bytes."""
+    _fields_ = [('status', ctypes.c_int32), ('obj_len', ctypes.c_uint32), ('plain_len', ctypes.c_uint32),
+                ('sig_len', ctypes.c_uint8), ('kind', ctypes.c_uint8), ('digest', ctypes.c_uint8),
+                ('reserved', ctypes.c_uint8), ('sig', ctypes.c_uint8 * 72), ('initial_hash', ctypes.c_uint8 * 64)]
+
+
+class BmpowTxLayout(ctypes.Structure):
+    """``bmpow_tx_layout`` (include/bmpow_tx.h)."""
+    _fields_ = [('slot_bytes', ctypes.c_uint64), ('body_at', ctypes.c_uint32), ('tail_at', ctypes.c_uint32),
+                ('plain_cap', ctypes.c_uint32), ('signed_len', ctypes.c_uint32), ('hash_blocks', ctypes.c_uint32),
+                ('reserved', ctypes.c_uint32)]
+
+
+class BmpowTxStats(ctypes.Structure):
+    """``bmpow_tx_stats`` (include/bmpow_tx.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('sets', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('pack_ms', ctypes.c_double), ('hash_ms', ctypes.c_double),
+                ('sign_ms', ctypes.c_double), ('ladder_ms', ctypes.c_double), ('seal_ms', ctypes.c_double),
+                ('finish_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_tx.h declares
+TX_SIGNATURES = [
+    ('bmpow_tx_objects', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, _p64, ctypes.c_char_p,
+      ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, _p64,
+      ctypes.c_void_p]),
+    ('bmpow_tx_layout_row', ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(BmpowTxLayout)]),
+    ('bmpow_tx_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowTxStats)]),
+    ('bmpow_tx_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -361,7 +395,7 @@ def load(path=None):
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
-                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES):
+                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

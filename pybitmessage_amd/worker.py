@@ -413,6 +413,111 @@ def send_msgs_signed(jobs, build_plain, rng=random, now=None, step_trials=0):
     return out
 
 
+
+# ------------------------------------------------------------------------------------------
+# the same with the signing, the encryption and the payload's hash in one library call (outgoing.py)
+# ------------------------------------------------------------------------------------------
+def broadcast_plaintext(address_version, stream, bitfield, pub_signing, pub_encryption, encoding, message, ntpb=None,
+                        extra=None):
+    """The unsigned body of a broadcast as ``sendBroadcast`` assembles it (``:625-640``): the sender's address
+    version and stream, the bitfield, the two public keys without their 0x04 prefix, for address version >= 3
+    the sender's own difficulty (the network defaults when None), the encoding and the length-prefixed
+    encoded message."""
+    payload = _varint(address_version) + _varint(stream) + bytes(bitfield)
+    payload += bytes(pub_signing)[-64:] + bytes(pub_encryption)[-64:]
+    if address_version >= 3:
+        n, e = _defaults(ntpb, extra)
+        payload += _varint(n) + _varint(e)
+    message = bytes(message)
+    return payload + _varint(encoding) + _varint(len(message)) + message
+
+
+def pubkey_plaintext(bitfield, pub_signing, pub_encryption, ntpb=None, extra=None):
+    """What a v3 or v4 pubkey's signature covers behind the object's header (``:348-369``, ``:422-443``): the
+    bitfield, the two public keys without their 0x04 prefix and the address's own difficulty (the network
+    defaults when None)."""
+    n, e = _defaults(ntpb, extra)
+    return bytes(bitfield) + bytes(pub_signing)[-64:] + bytes(pub_encryption)[-64:] + _varint(n) + _varint(e)
+
+
+class BuiltPowObject(PowObject):
+    """A :class:`PowObject` around a payload :func:`outgoing.build_objects` finished: ``initial_hash`` is the
+    SHA-512 the device computed behind the seal, not a second pass over the payload on the host."""
+
+    __slots__ = ('_initial_hash',)
+
+    def __init__(self, payload, initial_hash, ttl, ntpb=targets.networkDefaultProofOfWorkNonceTrialsPerByte,
+                 extra=targets.networkDefaultPayloadLengthExtraBytes, tag=None):
+        PowObject.__init__(self, payload, ttl, ntpb, extra, tag)
+        initial_hash = bytes(initial_hash)
+        if len(initial_hash) != 64:
+            raise ValueError('an initialHash is 64 bytes')
+        self._initial_hash = initial_hash
+
+    @property
+    def initial_hash(self):
+        return self._initial_hash
+
+
+def _pow_built(built, ttls, difficulties, n_jobs, step_trials):
+    """PoW the accepted rows of a :class:`outgoing.BuiltObjects`; None for every other job."""
+    objs = []
+    for i in built.accepted():
+        n, e = difficulties[i]
+        objs.append(BuiltPowObject(built.payload(i), built.initial_hash(i), ttls[i], n, e, tag=i))
+    out = [None] * n_jobs
+    for m, o in zip(objs, pow_objects(objs, step_trials)):
+        if len(o) <= MAX_OBJECT_SIZE:
+            out[m.tag] = o
+    return out
+
+
+def send_msgs_built(jobs, build_plain, rng=random, now=None, step_trials=0):
+    """:func:`send_msgs_signed` with one library call between the two proofs of work: ack PoW, then
+    :func:`outgoing.build_objects` signs, encrypts and hashes every msg on the device, then the msg PoW over
+    the device's ``initialHash``.  ``jobs`` and ``build_plain`` as for :func:`send_msgs_signed`, and the same
+    return value: the finished msg objects in job order; None for a msg whose recipient key is refused (the
+    reference's "encrypt didn't work"), whose signature came out zero, and for an object above 256 KiB."""
+    from . import outgoing
+    jobs = list(jobs)
+    want_ack = [k for k, (ackdata, _, _) in enumerate(jobs) if ackdata is not None]
+    packets = full_ack_messages([(jobs[k][0], jobs[k][1]) for k in want_ack], rng, now, step_trials)
+    ack_of = dict(zip(want_ack, packets))
+    made = [build_plain(ctx, ack_of.get(k, b'')) for k, (_, _, ctx) in enumerate(jobs)]
+    heads = [outgoing.msg_head(_embedded(ttl, now), stream) for _, _, _, _, stream, ttl, _, _ in made]
+    built = outgoing.build_objects([outgoing.SEALED] * len(made), heads, [bytes(b[0]) for b in made], [b[1] for b in made],
+                                   [b[2] for b in made], 'sha256')
+    for k in range(len(made)):
+        if built.status[k] == outgoing.BAD_RECIPIENT:
+            logger.warning("encrypt didn't work: the recipient's encryption key of msg %d is no good", k)
+    return _pow_built(built, [b[5] for b in made], [msg_difficulty(b[3], b[6], b[7]) for b in made], len(jobs), step_trials)
+
+
+def send_broadcasts(jobs, rng=random, now=None, step_trials=0, ntpb=None, extra=None):
+    """Batched ``sendBroadcast`` (``:599-681``).  ``jobs``: ``[(fields, ttl), ...]`` with ``fields`` an
+    :class:`outgoing.BroadcastFields` whose ``embeddedTime`` is filled here from the clamped, jittered TTL
+    (:func:`broadcast_ttl`).  One :func:`outgoing.build_broadcasts` call, then the PoW at ``_doPOWDefaults``'
+    target (``ntpb`` / ``extra``: the network defaults when None).  Returns the finished objects in job order,
+    None for one that could not be built or is above 256 KiB."""
+    from . import outgoing
+    jobs = list(jobs)
+    ttls = [broadcast_ttl(ttl, rng) for _, ttl in jobs]
+    built = outgoing.build_broadcasts([f._replace(embeddedTime=_embedded(t, now)) for (f, _), t in zip(jobs, ttls)])
+    return _pow_built(built, ttls, [_defaults(ntpb, extra)] * len(jobs), len(jobs), step_trials)
+
+
+def send_pubkeys(jobs, rng=random, now=None, step_trials=0, ntpb=None, extra=None):
+    """Batched ``sendOutOrStoreMyV3Pubkey`` / ``sendOutOrStoreMyV4Pubkey`` (``:331-378``, ``:416-470``).
+    ``jobs``: :class:`outgoing.PubkeyFields` rows of address version 3 or 4, ``embeddedTime`` filled here from
+    :func:`pubkey_ttl`.  One :func:`outgoing.build_pubkeys` call, then the PoW at ``_doPOWDefaults``' target.
+    Returns the finished objects in job order, None for one that could not be built."""
+    from . import outgoing
+    jobs = list(jobs)
+    ttls = [pubkey_ttl(rng) for _ in jobs]
+    built = outgoing.build_pubkeys([f._replace(embeddedTime=_embedded(t, now)) for f, t in zip(jobs, ttls)])
+    return _pow_built(built, ttls, [_defaults(ntpb, extra)] * len(jobs), len(jobs), step_trials)
+
+
 # ------------------------------------------------------------------------------------------
 # continuous batching across producer threads
 # ------------------------------------------------------------------------------------------

@@ -29,7 +29,7 @@ extern "C" {
 /* status: the first line of processmsg that returns */
 #define BMPOW_RX_OK 0                  /* reaches :582 */
 #define BMPOW_RX_MSG_VERSION 1         /* :444, also a header varint that does not decode */
-#define BMPOW_RX_NOT_MINE 2            /* :478 -- no key decrypts; never set by this library */
+#define BMPOW_RX_NOT_MINE 2            /* :478 -- no key decrypts; set by bmpow_rx_sealed_msgs (bmpow_rxopen.h) only */
 #define BMPOW_RX_SENDER_VERSION_0 3    /* :492 */
 #define BMPOW_RX_SENDER_VERSION_HIGH 4 /* :496 */
 #define BMPOW_RX_TOO_SHORT 5           /* :500 */

@@ -344,6 +344,29 @@ RXOBJ_SIGNATURES = [
 ]
 
 
+class BmpowRxSealedStats(ctypes.Structure):
+    """``bmpow_rx_sealed_stats`` (include/bmpow_rxopen.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('matched', ctypes.c_uint64),
+                ('sets', ctypes.c_uint64), ('launches', ctypes.c_uint64), ('rx_launches', ctypes.c_uint64),
+                ('bytes_up', ctypes.c_uint64), ('bytes_down', ctypes.c_uint64), ('match_ms', ctypes.c_double),
+                ('open_ms', ctypes.c_double), ('walk_ms', ctypes.c_double), ('hash_ms', ctypes.c_double),
+                ('scalar_ms', ctypes.c_double), ('curve_ms', ctypes.c_double), ('ident_ms', ctypes.c_double),
+                ('finish_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_rxopen.h declares
+RXOPEN_SIGNATURES = [
+    ('bmpow_rx_sealed_msgs', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_rx_sealed_plan', ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    ('bmpow_rx_sealed_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowRxSealedStats)]),
+    ('bmpow_rx_sealed_reset_stats', None, []),
+]
+
+
 class BmpowTxRec(ctypes.Structure):
     """``bmpow_tx_rec`` (include/bmpow_tx.h): one built object, 152 bytes."""
     _fields_ = [('status', ctypes.c_int32), ('obj_len', ctypes.c_uint32), ('plain_len', ctypes.c_uint32),
@@ -395,7 +418,8 @@ def load(path=None):
                                         'or make -C pybitmessage_amd/csrc)' % path)
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
-                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES):
+                            SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES +
+                            RXOPEN_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1,11 +1,8 @@
 // bmpow_host_ecies.hip -- the ECIES trial decryption's host side: payload parsing, key recoding, the
 // padded MAC pool, and the bmpow_ecdh / bmpow_ecies_* entry points (include/bmpow_ecies.h).
-#include "bmpow_host.h"
+#include "bmpow_host_ecies.h"
 
 #include <openssl/evp.h>
-
-#include "../../include/bmpow_ecies.h"
-#include "bmpow_ecies_kernels.h"
 
 // ---------------------------------------------------------------------------------------
 // One bmpow_ecies_match call: the well-formed objects, sorted by their MAC block count (descending, so a
@@ -17,14 +14,6 @@
 // when it returns); everything runs on the first shard's device and stream.
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
-
-constexpr size_t kSetObjects = 1u << 18;  // 4,096 waves: every SIMD of an MI355X holds its 4 even with one key
-constexpr size_t kSetPoolBytes = 256ull << 20;
-constexpr size_t kLaunchPairs = 1u << 21;  // ~30 ms of ladder
-
-struct U256 {
-  uint64_t w[4];  // little-endian words
-};
 
 constexpr uint64_t kFold = 0x1000003D1ULL;  // 2^256 mod p
 constexpr U256 kOrder = {{0xBFD25E8CD0364141ULL, 0xBAAEDCE6AF48A03BULL, 0xFFFFFFFFFFFFFFFEULL, 0xFFFFFFFFFFFFFFFFULL}};
@@ -92,11 +81,6 @@ ec::fe fe_from_u256(const U256& a) {
   return f;
 }
 
-struct Parsed {
-  U256 x, y;
-  size_t body_off;
-};
-
 // The reference's slicing (ECC.decrypt, _decode_pubkey) never fails on a length by itself; what it
 // leaves for a header that reaches into the last 32 bytes is a MAC shorter than 32 bytes or an unpack
 // error: never a match.  Well-formed: the header lies inside data[:-32].
@@ -147,18 +131,6 @@ void pad_mac_blocks(const uint8_t* data, size_t len, uint8_t* dst, uint32_t nblk
 
 bmpow_ecies_stats g_ecies_stats{};  // under g_mu
 
-struct EciesBufs {  // one call's buffers on the device
-  DevBuf<ec::ge> pts, tab;
-  DevBuf<uint32_t> ok;
-  DevBuf<int32_t> dig;
-  DevBuf<uint64_t> kout, key_e;
-  DevBuf<ec_obj> objs;
-  DevBuf<uint4> pool;
-  DevBuf<int> match;
-  DevBuf<ec::fe> x;
-  Event ev[3];
-};
-
 int ecies_events(EciesBufs& b, int dev) {
   for (Event& e : b.ev)
     if (!e) HIPTRY(e.alloc(dev));
@@ -172,11 +144,86 @@ int elapsed_into(double& acc, const Event& a, const Event& b) {
   return 0;
 }
 
-struct Item {  // a well-formed object
-  uint32_t orig;
-  uint32_t nblk;
-  Parsed hdr;
-};
+size_t ecies_set_end(const std::vector<Item>& items, size_t i0, uint64_t& blocks) {
+  size_t i1 = i0;
+  blocks = 0;
+  while (i1 < items.size() && i1 - i0 < kSetObjects && (i1 == i0 || (blocks + items[i1].nblk) * 64 <= kSetPoolBytes))
+    blocks += items[i1++].nblk;
+  return i1;
+}
+
+int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, uint32_t n, uint64_t blocks,
+                    const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys, bool want_key_e,
+                    bmpow_ecies_stats& st) {
+  if (blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "payload pool above 2^32 blocks");
+  const uint32_t stride = (n + EC_BLOCK - 1) / EC_BLOCK * EC_BLOCK;
+  std::vector<ec::ge>& pts = h.pts;
+  std::vector<ec_obj>& objs = h.objs;
+  std::vector<uint8_t>& pool = h.pool;
+  pts.resize(n);
+  objs.resize(n);
+  pool.resize(blocks * 64);
+  uint32_t blk = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    const Item& it = items[j];
+    pts[j].x = fe_from_u256(it.hdr.x);
+    pts[j].y = fe_from_u256(it.hdr.y);
+    objs[j].blk = blk;
+    objs[j].nblk = it.nblk;
+    blk += it.nblk;
+  }
+  bmsched::parallel_for(n, 1024, [&](size_t a, size_t e) {
+    for (size_t j = a; j < e; ++j) {
+      const Item& it = items[j];
+      const uint8_t* p = payloads[it.orig];
+      const size_t maced = lens[it.orig] - 32;
+      pad_mac_blocks(p, maced, pool.data() + (size_t)objs[j].blk * 64, it.nblk);
+      for (int w = 0; w < 8; ++w)
+        objs[j].mac[w] = (uint32_t)p[maced + 4 * w] << 24 | (uint32_t)p[maced + 4 * w + 1] << 16 |
+                         (uint32_t)p[maced + 4 * w + 2] << 8 | p[maced + 4 * w + 3];
+    }
+  });
+  const uint32_t kc = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_keys, kLaunchPairs / stride));
+  HIPTRY(b.pts.grow(sh.dev, stride));
+  HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
+  HIPTRY(b.ok.grow(sh.dev, stride));
+  HIPTRY(b.objs.grow(sh.dev, stride));
+  HIPTRY(b.match.grow(sh.dev, stride));
+  HIPTRY(b.pool.grow(sh.dev, std::max<size_t>(pool.size(), 64) / sizeof(uint4)));
+  HIPTRY(b.kout.grow(sh.dev, (size_t)8 * kc * stride));
+  if (want_key_e) HIPTRY(b.key_e.grow(sh.dev, (size_t)4 * stride));
+  HIPTRY(hipMemcpyAsync(b.pts.get(), pts.data(), n * sizeof(ec::ge), hipMemcpyHostToDevice, sh.stream));
+  HIPTRY(hipMemcpyAsync(b.objs.get(), objs.data(), n * sizeof(ec_obj), hipMemcpyHostToDevice, sh.stream));
+  HIPTRY(hipMemcpyAsync(b.pool.get(), pool.data(), pool.size(), hipMemcpyHostToDevice, sh.stream));
+  HIPTRY(hipMemsetAsync(b.match.get(), 0x7f, (size_t)stride * sizeof(int), sh.stream));
+  if (want_key_e) HIPTRY(hipMemsetAsync(b.key_e.get(), 0, (size_t)4 * stride * sizeof(uint64_t), sh.stream));
+  if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
+  HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
+  HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
+  HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
+  HIPTRY(hipStreamSynchronize(sh.stream));
+  if (const int rc = elapsed_into(st.prep_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+  for (size_t k0 = 0; k0 < n_keys; k0 += kc) {
+    if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
+    const uint32_t nk = (uint32_t)std::min<size_t>(kc, n_keys - k0);
+    HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
+    HIPTRY(ec_launch_keys(sh.stream, b.tab.get(), n, stride, b.dig.get() + k0 * EC_DIGITS, nk, b.kout.get()));
+    HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
+    HIPTRY(ec_launch_mac(sh.stream, b.kout.get(), n, stride, nk, b.objs.get(), b.pool.get(), b.ok.get(), (int)k0,
+                         b.match.get()));
+    if (want_key_e)
+      HIPTRY(ec_launch_gather(sh.stream, b.kout.get(), n, stride, nk, (int)k0, b.match.get(), b.key_e.get()));
+    HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
+    HIPTRY(hipStreamSynchronize(sh.stream));
+    if (const int rc = elapsed_into(st.ecdh_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+    if (const int rc = elapsed_into(st.mac_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
+    st.launches++;
+    st.pairs += (uint64_t)n * nk;
+  }
+  h.match.resize(n);
+  HIPTRY(hipMemcpyAsync(h.match.data(), b.match.get(), n * sizeof(int), hipMemcpyDeviceToHost, sh.stream));
+  return 0;
+}
 
 int ecies_match_locked(size_t n_obj, const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys,
                        const uint8_t* privkeys, int32_t* match, uint8_t* key_e_out) {
@@ -209,81 +256,17 @@ int ecies_match_locked(size_t n_obj, const uint8_t* const* payloads, const uint6
   HIPTRY(hipMemcpyAsync(b.dig.get(), dig.data(), dig.size() * sizeof(int32_t), hipMemcpyHostToDevice, sh.stream));
   g_ecies_stats.calls++;
 
-  std::vector<ec::ge> pts;
-  std::vector<ec_obj> objs;
-  std::vector<uint8_t> pool;
-  std::vector<int> hmatch;
+  EciesStage h;
   std::vector<uint64_t> hkeye;
   size_t i0 = 0;
   while (i0 < items.size()) {
-    size_t i1 = i0;
     uint64_t blocks = 0;
-    while (i1 < items.size() && i1 - i0 < kSetObjects && (i1 == i0 || (blocks + items[i1].nblk) * 64 <= kSetPoolBytes))
-      blocks += items[i1++].nblk;
-    if (blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "payload pool above 2^32 blocks");
-    const uint32_t n = (uint32_t)(i1 - i0), stride = (n + EC_BLOCK - 1) / EC_BLOCK * EC_BLOCK;
-    pts.resize(n);
-    objs.resize(n);
-    pool.resize(blocks * 64);
-    uint32_t blk = 0;
-    for (uint32_t j = 0; j < n; ++j) {
-      const Item& it = items[i0 + j];
-      pts[j].x = fe_from_u256(it.hdr.x);
-      pts[j].y = fe_from_u256(it.hdr.y);
-      objs[j].blk = blk;
-      objs[j].nblk = it.nblk;
-      blk += it.nblk;
-    }
-    bmsched::parallel_for(n, 1024, [&](size_t a, size_t e) {
-      for (size_t j = a; j < e; ++j) {
-        const Item& it = items[i0 + j];
-        const uint8_t* p = payloads[it.orig];
-        const size_t maced = lens[it.orig] - 32;
-        pad_mac_blocks(p, maced, pool.data() + (size_t)objs[j].blk * 64, it.nblk);
-        for (int w = 0; w < 8; ++w)
-          objs[j].mac[w] = (uint32_t)p[maced + 4 * w] << 24 | (uint32_t)p[maced + 4 * w + 1] << 16 |
-                           (uint32_t)p[maced + 4 * w + 2] << 8 | p[maced + 4 * w + 3];
-      }
-    });
-    const uint32_t kc = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_keys, kLaunchPairs / stride));
-    HIPTRY(b.pts.grow(sh.dev, stride));
-    HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
-    HIPTRY(b.ok.grow(sh.dev, stride));
-    HIPTRY(b.objs.grow(sh.dev, stride));
-    HIPTRY(b.match.grow(sh.dev, stride));
-    HIPTRY(b.pool.grow(sh.dev, std::max<size_t>(pool.size(), 64) / sizeof(uint4)));
-    HIPTRY(b.kout.grow(sh.dev, (size_t)8 * kc * stride));
-    if (key_e_out) HIPTRY(b.key_e.grow(sh.dev, (size_t)4 * stride));
-    HIPTRY(hipMemcpyAsync(b.pts.get(), pts.data(), n * sizeof(ec::ge), hipMemcpyHostToDevice, sh.stream));
-    HIPTRY(hipMemcpyAsync(b.objs.get(), objs.data(), n * sizeof(ec_obj), hipMemcpyHostToDevice, sh.stream));
-    HIPTRY(hipMemcpyAsync(b.pool.get(), pool.data(), pool.size(), hipMemcpyHostToDevice, sh.stream));
-    HIPTRY(hipMemsetAsync(b.match.get(), 0x7f, (size_t)stride * sizeof(int), sh.stream));
-    if (key_e_out) HIPTRY(hipMemsetAsync(b.key_e.get(), 0, (size_t)4 * stride * sizeof(uint64_t), sh.stream));
-    if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
-    HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
-    HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
-    HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
-    HIPTRY(hipStreamSynchronize(sh.stream));
-    if (const int rc = elapsed_into(g_ecies_stats.prep_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-    for (size_t k0 = 0; k0 < n_keys; k0 += kc) {
-      if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
-      const uint32_t nk = (uint32_t)std::min<size_t>(kc, n_keys - k0);
-      HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
-      HIPTRY(ec_launch_keys(sh.stream, b.tab.get(), n, stride, b.dig.get() + k0 * EC_DIGITS, nk, b.kout.get()));
-      HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
-      HIPTRY(ec_launch_mac(sh.stream, b.kout.get(), n, stride, nk, b.objs.get(), b.pool.get(), b.ok.get(), (int)k0,
-                           b.match.get()));
-      if (key_e_out)
-        HIPTRY(ec_launch_gather(sh.stream, b.kout.get(), n, stride, nk, (int)k0, b.match.get(), b.key_e.get()));
-      HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
-      HIPTRY(hipStreamSynchronize(sh.stream));
-      if (const int rc = elapsed_into(g_ecies_stats.ecdh_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-      if (const int rc = elapsed_into(g_ecies_stats.mac_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
-      g_ecies_stats.launches++;
-      g_ecies_stats.pairs += (uint64_t)n * nk;
-    }
-    hmatch.resize(n);
-    HIPTRY(hipMemcpyAsync(hmatch.data(), b.match.get(), n * sizeof(int), hipMemcpyDeviceToHost, sh.stream));
+    const size_t i1 = ecies_set_end(items, i0, blocks);
+    const uint32_t n = (uint32_t)(i1 - i0);
+    if (const int rc = ecies_match_set(sh, b, h, items.data() + i0, n, blocks, payloads, lens, n_keys, key_e_out != nullptr,
+                                       g_ecies_stats);
+        rc < 0)
+      return rc;
     if (key_e_out) {
       hkeye.resize((size_t)4 * n);
       HIPTRY(hipMemcpyAsync(hkeye.data(), b.key_e.get(), hkeye.size() * sizeof(uint64_t), hipMemcpyDeviceToHost,
@@ -291,7 +274,7 @@ int ecies_match_locked(size_t n_obj, const uint8_t* const* payloads, const uint6
     }
     HIPTRY(hipStreamSynchronize(sh.stream));
     for (uint32_t j = 0; j < n; ++j) {
-      const int m = hmatch[j];
+      const int m = h.match[j];
       if (m < 0 || (size_t)m >= n_keys) continue;
       const uint32_t orig = items[i0 + j].orig;
       match[orig] = m;

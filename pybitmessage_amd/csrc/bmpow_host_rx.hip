@@ -1,11 +1,8 @@
 // bmpow_host_rx.hip -- the msg processing's host side: the bmpow_rx_* entry points (include/bmpow_rx.h)
 // over the kernels of bmpow_rx.hip, bmpow_sig.hip, bmpow_ecies.hip (ec_prep_kernel) and bmpow_ident.hip.
-#include "bmpow_host_sig.h"
+#include "bmpow_host_rx.h"
 
-#include "../../include/bmpow_rx.h"
-#include "bmpow_ident_kernels.h"
 #include "bmpow_rx_fmt.h"
-#include "bmpow_rx_kernels.h"
 
 // ---------------------------------------------------------------------------------------
 // One call: the rows, sorted by the upper bound of their signed data's block count (descending, so a
@@ -17,20 +14,68 @@
 // The abort flag is read between sets.  The buffers are the call's own (DevBuf owners).
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
+
+int rx_grow_set(Shard& sh, SigBufs& b, RxBufs& x, uint32_t stride, uint64_t pool_chunks, uint64_t plain_chunks) {
+  HIPTRY(x.rows.grow(sh.dev, stride));
+  HIPTRY(x.plain.grow(sh.dev, plain_chunks));
+  HIPTRY(x.keys.grow(sh.dev, (size_t)8 * stride));
+  HIPTRY(x.recs.grow(sh.dev, stride));
+  HIPTRY(x.versions.grow(sh.dev, stride));
+  HIPTRY(x.streams.grow(sh.dev, stride));
+  HIPTRY(x.pk.grow(sh.dev, stride));
+  HIPTRY(x.flags.grow(sh.dev, stride));
+  HIPTRY(x.ident.grow(sh.dev, stride));
+  HIPTRY(b.sigs.grow(sh.dev, stride));
+  HIPTRY(b.pool.grow(sh.dev, pool_chunks));
+  HIPTRY(b.e.grow(sh.dev, (size_t)2 * stride));
+  HIPTRY(b.u1.grow(sh.dev, (size_t)2 * stride));
+  HIPTRY(b.dig.grow(sh.dev, (size_t)SG_DIGITS * stride));
+  HIPTRY(b.flip.grow(sh.dev, stride));
+  HIPTRY(b.tinf.grow(sh.dev, stride));
+  HIPTRY(b.verdict.grow(sh.dev, stride));
+  HIPTRY(b.pts.grow(sh.dev, stride));
+  HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
+  HIPTRY(b.ok.grow(sh.dev, stride));
+  HIPTRY(b.T.grow(sh.dev, stride));
+  return 0;
+}
+
+int rx_launch_set(Shard& sh, SigBufs& b, RxBufs& x, const ec::ge* comb, uint32_t n, uint32_t stride, uint64_t plain_chunks,
+                  uint64_t pool_chunks) {
+  const uint8_t* d_plain = reinterpret_cast<const uint8_t*>(x.plain.get());
+  HIPTRY(hipEventRecord(x.ev[0].get(), sh.stream));
+  HIPTRY(rx_launch_walk(sh.stream, x.rows.get(), d_plain, n, stride, x.recs.get(), b.sigs.get(), b.pts.get(),
+                        x.keys.get(), x.versions.get(), x.streams.get(), x.pk.get(), x.flags.get()));
+  HIPTRY(rx_launch_pack(sh.stream, x.rows.get(), x.plain.get(), plain_chunks, b.sigs.get(), x.pk.get(), n, b.pool.get(),
+                        pool_chunks));
+  HIPTRY(hipEventRecord(x.ev[1].get(), sh.stream));
+  HIPTRY(sg_launch_hash(sh.stream, b.sigs.get(), b.pool.get(), n, stride, b.e.get()));
+  HIPTRY(hipEventRecord(x.ev[2].get(), sh.stream));
+  HIPTRY(sg_launch_scalars(sh.stream, b.sigs.get(), b.e.get(), n, stride, 2, b.u1.get(), b.dig.get(), b.flip.get()));
+  HIPTRY(hipEventRecord(x.ev[3].get(), sh.stream));
+  HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
+  HIPTRY(sg_launch_ladder(sh.stream, b.tab.get(), n, stride, b.dig.get(), b.flip.get(), b.T.get(), b.tinf.get()));
+  HIPTRY(sg_launch_comb(sh.stream, comb, b.sigs.get(), b.u1.get(), b.T.get(), b.tinf.get(), b.ok.get(), n, stride, 2,
+                        b.verdict.get()));
+  HIPTRY(hipEventRecord(x.ev[4].get(), sh.stream));
+  HIPTRY(id_launch_derive(sh.stream, x.keys.get(), x.versions.get(), x.streams.get(), n, x.ident.get()));
+  HIPTRY(hipEventRecord(x.ev[5].get(), sh.stream));
+  HIPTRY(rx_launch_finish(sh.stream, x.rows.get(), d_plain, b.verdict.get(), x.flags.get(), x.ident.get(), n,
+                          x.recs.get()));
+  HIPTRY(hipEventRecord(x.ev[6].get(), sh.stream));
+  return 0;
+}
+
+int rx_phase_times(const RxBufs& x, bmpow_rx_stats& st) {
+  double* const acc[6] = {&st.walk_ms, &st.hash_ms, &st.scalar_ms, &st.curve_ms, &st.ident_ms, &st.finish_ms};
+  for (int k = 0; k < 6; ++k)
+    if (const int rc = sig_elapsed(*acc[k], x.ev[k], x.ev[k + 1]); rc < 0) return rc;
+  return 0;
+}
+
 namespace {
 
 bmpow_rx_stats g_rx_stats{};  // under g_mu
-
-struct RxBufs {
-  DevBuf<rx_row> rows;
-  DevBuf<uint4> plain, keys;
-  DevBuf<bmpow_rx_msg_rec> recs;
-  DevBuf<uint64_t> versions, streams;
-  DevBuf<rx_pk> pk;
-  DevBuf<uint8_t> flags;
-  DevBuf<bmpow_ident_rec> ident;
-  Event ev[7];
-};
 
 struct RxItem {
   uint32_t orig;
@@ -90,57 +135,14 @@ int rx_run_locked(size_t n_all, const uint8_t* const* objs, const uint64_t* obj_
       }
     });
     const uint64_t pool_chunks = std::max<uint64_t>(blocks * 4, 4), plain_chunks = plain_bytes / 16;
-    HIPTRY(x.rows.grow(sh.dev, stride));
-    HIPTRY(x.plain.grow(sh.dev, plain_chunks));
-    HIPTRY(x.keys.grow(sh.dev, (size_t)8 * stride));
-    HIPTRY(x.recs.grow(sh.dev, stride));
-    HIPTRY(x.versions.grow(sh.dev, stride));
-    HIPTRY(x.streams.grow(sh.dev, stride));
-    HIPTRY(x.pk.grow(sh.dev, stride));
-    HIPTRY(x.flags.grow(sh.dev, stride));
-    HIPTRY(x.ident.grow(sh.dev, stride));
-    HIPTRY(b.sigs.grow(sh.dev, stride));
-    HIPTRY(b.pool.grow(sh.dev, pool_chunks));
-    HIPTRY(b.e.grow(sh.dev, (size_t)2 * stride));
-    HIPTRY(b.u1.grow(sh.dev, (size_t)2 * stride));
-    HIPTRY(b.dig.grow(sh.dev, (size_t)SG_DIGITS * stride));
-    HIPTRY(b.flip.grow(sh.dev, stride));
-    HIPTRY(b.tinf.grow(sh.dev, stride));
-    HIPTRY(b.verdict.grow(sh.dev, stride));
-    HIPTRY(b.pts.grow(sh.dev, stride));
-    HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
-    HIPTRY(b.ok.grow(sh.dev, stride));
-    HIPTRY(b.T.grow(sh.dev, stride));
+    if (const int rc = rx_grow_set(sh, b, x, stride, pool_chunks, plain_chunks); rc < 0) return rc;
     HIPTRY(hipMemcpyAsync(x.rows.get(), rows.data(), n * sizeof(rx_row), hipMemcpyHostToDevice, sh.stream));
     HIPTRY(hipMemcpyAsync(x.plain.get(), stage.data(), plain_bytes, hipMemcpyHostToDevice, sh.stream));
-    const uint8_t* d_plain = reinterpret_cast<const uint8_t*>(x.plain.get());
-    HIPTRY(hipEventRecord(x.ev[0].get(), sh.stream));
-    HIPTRY(rx_launch_walk(sh.stream, x.rows.get(), d_plain, n, stride, x.recs.get(), b.sigs.get(), b.pts.get(),
-                          x.keys.get(), x.versions.get(), x.streams.get(), x.pk.get(), x.flags.get()));
-    HIPTRY(rx_launch_pack(sh.stream, x.rows.get(), x.plain.get(), plain_chunks, b.sigs.get(), x.pk.get(), n, b.pool.get(),
-                          pool_chunks));
-    HIPTRY(hipEventRecord(x.ev[1].get(), sh.stream));
-    HIPTRY(sg_launch_hash(sh.stream, b.sigs.get(), b.pool.get(), n, stride, b.e.get()));
-    HIPTRY(hipEventRecord(x.ev[2].get(), sh.stream));
-    HIPTRY(sg_launch_scalars(sh.stream, b.sigs.get(), b.e.get(), n, stride, 2, b.u1.get(), b.dig.get(), b.flip.get()));
-    HIPTRY(hipEventRecord(x.ev[3].get(), sh.stream));
-    HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
-    HIPTRY(sg_launch_ladder(sh.stream, b.tab.get(), n, stride, b.dig.get(), b.flip.get(), b.T.get(), b.tinf.get()));
-    HIPTRY(sg_launch_comb(sh.stream, comb, b.sigs.get(), b.u1.get(), b.T.get(), b.tinf.get(), b.ok.get(), n, stride, 2,
-                          b.verdict.get()));
-    HIPTRY(hipEventRecord(x.ev[4].get(), sh.stream));
-    HIPTRY(id_launch_derive(sh.stream, x.keys.get(), x.versions.get(), x.streams.get(), n, x.ident.get()));
-    HIPTRY(hipEventRecord(x.ev[5].get(), sh.stream));
-    HIPTRY(rx_launch_finish(sh.stream, x.rows.get(), d_plain, b.verdict.get(), x.flags.get(), x.ident.get(), n,
-                            x.recs.get()));
-    HIPTRY(hipEventRecord(x.ev[6].get(), sh.stream));
+    if (const int rc = rx_launch_set(sh, b, x, comb, n, stride, plain_chunks, pool_chunks); rc < 0) return rc;
     recs.resize(n);
     HIPTRY(hipMemcpyAsync(recs.data(), x.recs.get(), n * sizeof(bmpow_rx_msg_rec), hipMemcpyDeviceToHost, sh.stream));
     HIPTRY(hipStreamSynchronize(sh.stream));
-    double* const acc[6] = {&g_rx_stats.walk_ms,  &g_rx_stats.hash_ms,  &g_rx_stats.scalar_ms,
-                            &g_rx_stats.curve_ms, &g_rx_stats.ident_ms, &g_rx_stats.finish_ms};
-    for (int k = 0; k < 6; ++k)
-      if (const int rc = sig_elapsed(*acc[k], x.ev[k], x.ev[k + 1]); rc < 0) return rc;
+    if (const int rc = rx_phase_times(x, g_rx_stats); rc < 0) return rc;
     for (uint32_t j = 0; j < n; ++j) out[items[i0 + j].orig] = recs[j];
     g_rx_stats.sets++;
     g_rx_stats.launches += 9;

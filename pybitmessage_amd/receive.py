@@ -5,7 +5,10 @@ fields, checks its signature, and hashes the sender's keys into the ripe and the
 decryption that is one call on the device (:func:`open_msgs`, ``bmpow_rx_msgs``, ``include/bmpow_rx.h``): the
 walk, the signed data, both digests, the curve equation, the ripe, the address and ``sigHash`` give one
 record per msg whose status names the first line of ``processmsg`` that returns; :func:`process_msgs` puts
-:func:`ecies.process_msgs` in front of it.
+:func:`ecies.process_msgs` in front of it.  :func:`open_sealed_msgs` / :func:`process_sealed_msgs` do both in one
+library call (``bmpow_rx_sealed_msgs``, ``include/bmpow_rxopen.h``): the matched ciphertexts are decrypted where
+the MAC kernel hashed them, into the pool the walk reads, so no ciphertext crosses the bus twice, ``key_e``
+never reaches the host and a plaintext crosses once, downwards.
 
 ``class_objectProcessor.processbroadcast`` (``src/class_objectProcessor.py:749-973``) and
 ``protocol.decryptAndCheckPubkeyPayload`` (``src/protocol.py:401-518``) decrypt an object with a key derived
@@ -184,8 +187,11 @@ class OpenedMsgs(object):
     walked fields of a row are filled as far as ``processmsg`` gets before it returns; ``ripe``,
     ``fromAddress`` and ``sigHash`` belong to rows whose status is ``OK``."""
 
-    def __init__(self, recs, plaintexts):
+    def __init__(self, recs, plaintexts, match=None, ripes=None):
         self.recs, self.plaintexts = recs, plaintexts
+        # :func:`open_sealed_msgs` only: per row the index of the key whose MAC verified (-1: none), and the
+        # ripes those indices name
+        self.match, self._ripes = match, ripes
         self.status, self.digest = recs['status'], recs['digest']
         self.senderVersion, self.senderStream = recs['sender_version'], recs['sender_stream']
         self.encoding, self.behaviour = recs['encoding'], recs['behaviour']
@@ -221,6 +227,13 @@ class OpenedMsgs(object):
 
     def sigHash(self, i):
         return self.recs[i]['sig_hash'].tobytes()
+
+    def toRipe(self, i):
+        """The ripe of the key that opened row ``i`` (``:471``), None where no key's MAC verified; for batches
+        of :func:`open_sealed_msgs`."""
+        if self.match is None:
+            raise ValueError('only a batch of open_sealed_msgs knows its keys')
+        return self._ripes[int(self.match[i])] if self.match[i] >= 0 else None
 
     def accepted(self):
         """The rows ``processmsg`` would go on with at ``:582``."""
@@ -294,6 +307,119 @@ def process_msgs(objects, keys_by_ripe):
                            res.signature(j), int(r['digest']), res.pubkeyData(j), res.fromAddress(j), res.ripe(j),
                            res.sigHash(j))
     return out
+
+
+class _ArenaPlaintexts(object):
+    """The plaintexts of :func:`open_sealed_msgs` as a sequence of bytes, each cut from the call's arena when it
+    is asked for; ``b''`` for a row without one."""
+
+    def __init__(self, arena, offs, lens):
+        self._arena, self._offs, self._lens = arena, offs, lens
+
+    def __len__(self):
+        return len(self._lens)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        off, n = int(self._offs[i]), int(self._lens[i])
+        return self._arena[off:off + n].tobytes()
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def __eq__(self, other):
+        return list(self) == list(other)
+
+    def __ne__(self, other):
+        return not self == other
+
+
+def _sealed_keys(keys_by_ripe):
+    """``(ripes, 32-byte keys)`` of a mapping ripe -> private encryption key, or of a pair ``(ripes, privkeys)``
+    of equally long sequences (which may try one key under two ripes)."""
+    if hasattr(keys_by_ripe, 'keys'):
+        ripes = list(keys_by_ripe)
+        privs = [keys_by_ripe[r] for r in ripes]
+    else:
+        ripes, privs = keys_by_ripe
+        ripes, privs = list(ripes), list(privs)
+    if len(ripes) != len(privs):
+        raise ValueError('one ripe per private key')
+    ripes = [r if type(r) is bytes else bytes(r) for r in ripes]
+    if any(len(r) != 20 for r in ripes):
+        raise ValueError('a ripe is 20 bytes')
+    return ripes, [ecies._key32(k) for k in privs]
+
+
+def open_sealed_msgs(objects, keys_by_ripe):
+    """``processmsg`` from ``:441`` to ``:591`` for msg objects as they came off the wire, in one call on the
+    device (``bmpow_rx_sealed_msgs``, ``include/bmpow_rxopen.h``): the trial decryption against every key, the
+    AES pass of the rows whose MAC verified and everything of :func:`open_msgs` behind it, with no ciphertext
+    uploaded twice and no key or plaintext on the host in between.  ``keys_by_ripe`` as for
+    :func:`process_msgs` (or a pair ``(ripes, privkeys)``).  Gives an :class:`OpenedMsgs` over every object:
+    ``status`` is ``MSG_VERSION`` where the head refuses, ``NOT_MINE`` where no key opens it (``:478``), else
+    what :func:`open_msgs` says; ``match[i]`` is the index of the key whose MAC verified (-1: none),
+    ``toRipe(i)`` its ripe, ``plaintexts[i]`` the decrypted payload (``b''`` where there is none)."""
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    ripes, privs = _sealed_keys(keys_by_ripe)
+    n = len(objs)
+    recs = np.zeros(n, dtype=MSG_REC)
+    match = np.full(n, -1, dtype=np.int32)
+    offs, lens = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    if n == 0:
+        return OpenedMsgs(recs, [], match, ripes)
+    lib = _lib.get()
+    op = (ctypes.c_char_p * n)(*objs)
+    ol = np.fromiter(map(len, objs), dtype=np.uint64, count=n)
+    arena = np.empty(max(int(ol.sum()), 1), dtype=np.uint8)  # untouched pages cost nothing
+    _lib.check(lib, lib.bmpow_rx_sealed_msgs(n, ctypes.cast(op, ctypes.c_void_p), ol.ctypes.data_as(signatures._P64),
+                                             len(privs), b''.join(privs), b''.join(ripes), recs.ctypes.data,
+                                             match.ctypes.data, arena.ctypes.data, arena.size, offs.ctypes.data,
+                                             lens.ctypes.data), 'bmpow_rx_sealed_msgs')
+    return OpenedMsgs(recs, _ArenaPlaintexts(arena, offs, lens), match, ripes)
+
+
+def process_sealed_msgs(objects, keys_by_ripe):
+    """:func:`process_msgs` by way of :func:`open_sealed_msgs`: the same list of :class:`Msg` / None."""
+    res = open_sealed_msgs(objects, keys_by_ripe)
+    out = [None] * len(res)
+    for j in res.accepted():
+        r = res.recs[j]
+        out[j] = Msg(res.toRipe(j), int(r['sender_version']), int(r['sender_stream']), r['behaviour'].tobytes(),
+                     int(r['ntpb']), int(r['extra']), int(r['encoding']), res.message(j), res.ackData(j),
+                     res.signature(j), int(r['digest']), res.pubkeyData(j), res.fromAddress(j), res.ripe(j),
+                     res.sigHash(j))
+    return out
+
+
+def sealed_plan(obj):
+    """What :func:`open_sealed_msgs` does with one object before any key is tried, on the host
+    (``bmpow_rx_sealed_plan``): ``(openable, reason, payload_off, body_off, clen)`` with ``reason`` one of
+    ``PLAN_OK``, ``PLAN_HEAD`` (the head refuses), ``PLAN_PAYLOAD`` (malformed payload) and ``PLAN_CIPHER`` (the
+    ciphertext is empty or no multiple of 16 bytes)."""
+    lib = _lib.host()
+    obj = obj if type(obj) is bytes else bytes(obj)
+    po, bo, cl = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    reason = ctypes.c_int(0)
+    rc = _lib.check(lib, lib.bmpow_rx_sealed_plan(obj, len(obj), ctypes.byref(po), ctypes.byref(bo), ctypes.byref(cl),
+                                                  ctypes.byref(reason)), 'bmpow_rx_sealed_plan')
+    return rc == 1, reason.value, po.value, bo.value, cl.value
+
+
+PLAN_OK, PLAN_HEAD, PLAN_PAYLOAD, PLAN_CIPHER = 0, 1, 2, 3
+
+
+def sealed_stats():
+    """The counters of ``bmpow_rx_sealed_msgs`` (``bmpow_rx_sealed_stats``) as a dict."""
+    lib = _lib.get()
+    st = _lib.BmpowRxSealedStats()
+    _lib.check(lib, lib.bmpow_rx_sealed_get_stats(ctypes.byref(st)), 'bmpow_rx_sealed_get_stats')
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def sealed_reset_stats():
+    _lib.get().bmpow_rx_sealed_reset_stats()
 
 
 def ack_has_valid_header(ackData):

@@ -7,6 +7,7 @@
 
 #include "../../include/bmpow_ecies.h"
 #include "bmpow_ecies_kernels.h"
+#include "bmpow_set_plan.h"
 
 namespace bmhost {
 

@@ -145,11 +145,9 @@ int elapsed_into(double& acc, const Event& a, const Event& b) {
 }
 
 size_t ecies_set_end(const std::vector<Item>& items, size_t i0, uint64_t& blocks) {
-  size_t i1 = i0;
-  blocks = 0;
-  while (i1 < items.size() && i1 - i0 < kSetObjects && (i1 == i0 || (blocks + items[i1].nblk) * 64 <= kSetPoolBytes))
-    blocks += items[i1++].nblk;
-  return i1;
+  const SetCut cut = plan_set(items, i0, [](const Item& it) { return it.nblk; }, kSetObjects, kSetPoolBytes);
+  blocks = cut.blocks;
+  return cut.i1;
 }
 
 int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, uint32_t n, uint64_t blocks,

@@ -1,6 +1,6 @@
 // bmpow_host_rxopen.hip -- the one-call opening of received msgs: the bmpow_rx_sealed_* entry points
 // (include/bmpow_rxopen.h) over the ECIES set of bmpow_host_ecies.hip, the opening kernel of bmpow_rxopen.hip
-// and the msg-processing set of bmpow_host_rx.hip.
+// and the msg family's set of the rows pipeline (bmpow_host_rx.h, bmpow_host_rows.h).
 #include "bmpow_host_ecies.h"
 #include "bmpow_host_rx.h"
 
@@ -14,9 +14,9 @@
 // of bmpow_ecies_match: per set ecies_match_set uploads the padded MAC pool once and runs the preparation,
 // ladder, MAC and gather launches for every key group.  match[] of the set comes down (4 bytes per row); for
 // the rows it names whose ciphertext is a positive multiple of 16 bytes the host builds compacted rx_rows
-// and rxo_rows (96 bytes per matched row) and uploads only those.  rxo_open_kernel then decrypts each from the
-// MAC pool into the plaintext pool and writes the row's plen, and the nine launches of rx_launch_set read that
-// pool where it lies.  Down come the matched rows' records, opened[] and the plaintext pool, in one copy each.
+// and rxs_rows (96 bytes per matched row) and uploads only those.  rxs_open_kernel then decrypts each from the
+// MAC pool into the plaintext pool and writes the row's plen, and the nine launches of launch_set
+// (bmpow_host_rows.h) read that pool where it lies.  Down come the matched rows' records, opened[] and the plaintext pool, in one copy each.
 // A set without a matched row launches none of the ten.  The abort flag is read between sets and (by
 // ecies_match_set) between key groups.  The buffers are the call's own (DevBuf owners).
 // ---------------------------------------------------------------------------------------
@@ -47,7 +47,7 @@ bool walk_head(const uint8_t* obj, uint64_t len, bmpow_rx_msg_rec& rec, size_t& 
 }
 
 struct SealedBufs {
-  DevBuf<rxo_row> orows;
+  DevBuf<rxs_row> orows;
   DevBuf<int32_t> opened;
   Event ev[2];
 };
@@ -72,7 +72,7 @@ int sealed_run_locked(const std::vector<Item>& items, const uint8_t* const* payl
   SealedBufs o;
   EciesStage h;
   std::vector<rx_row> rows;
-  std::vector<rxo_row> orows;
+  std::vector<rxs_row> orows;
   std::vector<uint32_t> who;  // the input index of each matched row
   std::vector<bmpow_rx_msg_rec> drecs;
   std::vector<int32_t> opened;
@@ -110,7 +110,7 @@ int sealed_run_locked(const std::vector<Item>& items, const uint8_t* const* payl
       std::memcpy(r.head, objs[orig], r.hlen);
       std::memcpy(r.to_ripe, ripes + 20 * (size_t)m, 20);
       rows.push_back(r);
-      orows.push_back(rxo_row{j, h.objs[j].blk, (uint32_t)it.hdr.body_off, (uint32_t)clen});
+      orows.push_back(rxs_row{j, h.objs[j].blk, (uint32_t)it.hdr.body_off, (uint32_t)clen});
       who.push_back(orig);
       poff += clen;
       blk += rxf::signed_blocks_bound(clen - 1);  // the plaintext is at least one byte shorter
@@ -128,17 +128,17 @@ int sealed_run_locked(const std::vector<Item>& items, const uint8_t* const* payl
       const uint32_t stride = (nm + SG_BLOCK - 1) / SG_BLOCK * SG_BLOCK;
       const uint64_t plain_bytes = std::max<uint64_t>(poff, 16), plain_chunks = plain_bytes / 16;
       const uint64_t pool_chunks = std::max<uint64_t>(blk * 4, 4);
-      if (const int rc = rx_grow_set(sh, sb, x, stride, pool_chunks, plain_chunks); rc < 0) return rc;
+      if (const int rc = grow_set(sh, sb, x, stride, pool_chunks, plain_chunks); rc < 0) return rc;
       HIPTRY(o.orows.grow(sh.dev, stride));
       HIPTRY(o.opened.grow(sh.dev, stride));
       HIPTRY(hipMemcpyAsync(x.rows.get(), rows.data(), nm * sizeof(rx_row), hipMemcpyHostToDevice, sh.stream));
-      HIPTRY(hipMemcpyAsync(o.orows.get(), orows.data(), nm * sizeof(rxo_row), hipMemcpyHostToDevice, sh.stream));
+      HIPTRY(hipMemcpyAsync(o.orows.get(), orows.data(), nm * sizeof(rxs_row), hipMemcpyHostToDevice, sh.stream));
       HIPTRY(hipEventRecord(o.ev[0].get(), sh.stream));
-      HIPTRY(rxo_launch_open(sh.stream, o.orows.get(), b.key_e.get(), n, reinterpret_cast<const uint8_t*>(b.pool.get()),
+      HIPTRY(rxs_launch_open(sh.stream, o.orows.get(), b.key_e.get(), n, reinterpret_cast<const uint8_t*>(b.pool.get()),
                              h.pool.size(), x.rows.get(), reinterpret_cast<uint8_t*>(x.plain.get()), plain_bytes, nm,
                              o.opened.get()));
       HIPTRY(hipEventRecord(o.ev[1].get(), sh.stream));
-      if (const int rc = rx_launch_set(sh, sb, x, comb, nm, stride, plain_chunks, pool_chunks); rc < 0) return rc;
+      if (const int rc = launch_set(sh, sb, x, comb, nm, stride, plain_chunks, pool_chunks); rc < 0) return rc;
       drecs.resize(nm);
       opened.resize(nm);
       plain.resize(poff);
@@ -148,13 +148,13 @@ int sealed_run_locked(const std::vector<Item>& items, const uint8_t* const* payl
       HIPTRY(hipStreamSynchronize(sh.stream));
       if (const int rc = sig_elapsed(st.open_ms, o.ev[0], o.ev[1]); rc < 0) return rc;
       bmpow_rx_stats rs{};
-      if (const int rc = rx_phase_times(x, rs); rc < 0) return rc;
+      if (const int rc = phase_times(x, rs); rc < 0) return rc;
       st.walk_ms += rs.walk_ms, st.hash_ms += rs.hash_ms, st.scalar_ms += rs.scalar_ms;
       st.curve_ms += rs.curve_ms, st.ident_ms += rs.ident_ms, st.finish_ms += rs.finish_ms;
       st.matched += nm;
       st.launches += 10;
       st.rx_launches += 10;
-      st.bytes_up += (uint64_t)nm * (sizeof(rx_row) + sizeof(rxo_row));
+      st.bytes_up += (uint64_t)nm * (sizeof(rx_row) + sizeof(rxs_row));
       st.bytes_down += (uint64_t)nm * (sizeof(bmpow_rx_msg_rec) + sizeof(int32_t)) + poff;
       bmsched::parallel_for(nm, 1024, [&](size_t a, size_t z) {
         for (size_t k = a; k < z; ++k) {

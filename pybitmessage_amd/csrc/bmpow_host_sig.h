@@ -1,11 +1,13 @@
-// bmpow_host_sig.h -- what the host units that run the signature kernels share (internal): the set limits
-// and one call's device buffers.  Used by bmpow_host_sig.hip (bmpow_sig_verify, bmpow_ecdsa_verify_digest)
-// and bmpow_host_rx.hip (bmpow_rx_msgs); the fixed-base comb table they both pass to sg_launch_comb is
-// addr_comb16_table (bmpow_host.h).
+// bmpow_host_sig.h -- what the host units that run the signature kernels share (internal): the set limits,
+// one call's device buffers and the verification launches of a set.  Used by bmpow_host_sig.hip
+// (bmpow_sig_verify, bmpow_ecdsa_verify_digest) and, through bmpow_host_rows.h, by bmpow_host_rx.hip
+// (bmpow_rx_msgs), bmpow_host_rxobj.hip (bmpow_rx_objects) and bmpow_host_rxopen.hip (bmpow_rx_sealed_msgs);
+// the fixed-base comb table they all pass on is addr_comb16_table (bmpow_host.h).
 #pragma once
 #include "bmpow_host.h"
 
 #include "bmpow_ecies_kernels.h"
+#include "bmpow_set_plan.h"
 #include "bmpow_sig_kernels.h"
 
 namespace bmhost {
@@ -24,7 +26,15 @@ struct SigBufs {  // one call's buffers on the device
   DevBuf<uint32_t> ok;
   DevBuf<sg_pt> T;
   Event ev[4];
+
+  // Room for a set of stride rows (a multiple of SG_BLOCK) and pool_chunks of padded blocks in 16-byte units.
+  int grow(Shard& sh, uint32_t stride, uint64_t pool_chunks);
 };
+
+// What follows the hash on sh.stream: scalars, key tables (ec_prep_kernel), ladder and combs, four launches
+// over sigs, e and pts of n rows.  Between the scalars and the key tables `mid` is recorded: the boundary of
+// every caller's scalar and curve phases.  The events around the four are the caller's own.
+int sig_launch_verify(Shard& sh, SigBufs& b, const ec::ge* comb, uint32_t n, uint32_t stride, int nhash, const Event& mid);
 
 inline int sig_elapsed(double& acc, const Event& a, const Event& b) {
   float ms = 0;

@@ -14,6 +14,33 @@
 // everything runs on the first shard's device and stream.
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
+
+int SigBufs::grow(Shard& sh, uint32_t stride, uint64_t pool_chunks) {
+  HIPTRY(sigs.grow(sh.dev, stride));
+  HIPTRY(pool.grow(sh.dev, pool_chunks));
+  HIPTRY(e.grow(sh.dev, (size_t)2 * stride));
+  HIPTRY(u1.grow(sh.dev, (size_t)2 * stride));
+  HIPTRY(dig.grow(sh.dev, (size_t)SG_DIGITS * stride));
+  HIPTRY(flip.grow(sh.dev, stride));
+  HIPTRY(tinf.grow(sh.dev, stride));
+  HIPTRY(verdict.grow(sh.dev, stride));
+  HIPTRY(pts.grow(sh.dev, stride));
+  HIPTRY(tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
+  HIPTRY(ok.grow(sh.dev, stride));
+  HIPTRY(T.grow(sh.dev, stride));
+  return 0;
+}
+
+int sig_launch_verify(Shard& sh, SigBufs& b, const ec::ge* comb, uint32_t n, uint32_t stride, int nhash, const Event& mid) {
+  HIPTRY(sg_launch_scalars(sh.stream, b.sigs.get(), b.e.get(), n, stride, nhash, b.u1.get(), b.dig.get(), b.flip.get()));
+  HIPTRY(hipEventRecord(mid.get(), sh.stream));
+  HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
+  HIPTRY(sg_launch_ladder(sh.stream, b.tab.get(), n, stride, b.dig.get(), b.flip.get(), b.T.get(), b.tinf.get()));
+  HIPTRY(sg_launch_comb(sh.stream, comb, b.sigs.get(), b.u1.get(), b.T.get(), b.tinf.get(), b.ok.get(), n, stride, nhash,
+                        b.verdict.get()));
+  return 0;
+}
+
 namespace {
 
 using sn::sc;
@@ -109,11 +136,8 @@ int sig_run_locked(std::vector<SigItem>& items, int nhash, const uint8_t* const*
   size_t i0 = 0;
   while (i0 < items.size()) {
     if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
-    size_t i1 = i0;
-    uint64_t blocks = 0;
-    while (i1 < items.size() && i1 - i0 < kSigSetObjects &&
-           (i1 == i0 || (blocks + items[i1].nblk) * 64 <= kSigSetPoolBytes))
-      blocks += items[i1++].nblk;
+    const auto [i1, blocks] =
+        plan_set(items, i0, [](const SigItem& it) { return it.nblk; }, kSigSetObjects, kSigSetPoolBytes);
     if (blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "message pool above 2^32 blocks");
     const uint32_t n = (uint32_t)(i1 - i0), stride = (n + SG_BLOCK - 1) / SG_BLOCK * SG_BLOCK;
     sigs.resize(n);
@@ -141,18 +165,7 @@ int sig_run_locked(std::vector<SigItem>& items, int nhash, const uint8_t* const*
       e.resize(n);
       for (uint32_t j = 0; j < n; ++j) e[j] = sc_from_be(digests + 32 * (size_t)items[i0 + j].orig);
     }
-    HIPTRY(b.sigs.grow(sh.dev, stride));
-    HIPTRY(b.pool.grow(sh.dev, std::max<size_t>(pool.size(), 64) / sizeof(uint4)));
-    HIPTRY(b.e.grow(sh.dev, (size_t)2 * stride));
-    HIPTRY(b.u1.grow(sh.dev, (size_t)2 * stride));
-    HIPTRY(b.dig.grow(sh.dev, (size_t)SG_DIGITS * stride));
-    HIPTRY(b.flip.grow(sh.dev, stride));
-    HIPTRY(b.tinf.grow(sh.dev, stride));
-    HIPTRY(b.verdict.grow(sh.dev, stride));
-    HIPTRY(b.pts.grow(sh.dev, stride));
-    HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
-    HIPTRY(b.ok.grow(sh.dev, stride));
-    HIPTRY(b.T.grow(sh.dev, stride));
+    if (const int rc = b.grow(sh, stride, std::max<size_t>(pool.size(), 64) / sizeof(uint4)); rc < 0) return rc;
     HIPTRY(hipMemcpyAsync(b.sigs.get(), sigs.data(), n * sizeof(sg_sig), hipMemcpyHostToDevice, sh.stream));
     HIPTRY(hipMemcpyAsync(b.pts.get(), pts.data(), n * sizeof(ec::ge), hipMemcpyHostToDevice, sh.stream));
     if (nhash == 2) {
@@ -164,13 +177,7 @@ int sig_run_locked(std::vector<SigItem>& items, int nhash, const uint8_t* const*
     HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
     if (nhash == 2) HIPTRY(sg_launch_hash(sh.stream, b.sigs.get(), b.pool.get(), n, stride, b.e.get()));
     HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
-    HIPTRY(sg_launch_scalars(sh.stream, b.sigs.get(), b.e.get(), n, stride, nhash, b.u1.get(), b.dig.get(),
-                             b.flip.get()));
-    HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
-    HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
-    HIPTRY(sg_launch_ladder(sh.stream, b.tab.get(), n, stride, b.dig.get(), b.flip.get(), b.T.get(), b.tinf.get()));
-    HIPTRY(sg_launch_comb(sh.stream, comb, b.sigs.get(), b.u1.get(), b.T.get(), b.tinf.get(), b.ok.get(), n, stride,
-                          nhash, b.verdict.get()));
+    if (const int rc = sig_launch_verify(sh, b, comb, n, stride, nhash, b.ev[2]); rc < 0) return rc;
     HIPTRY(hipEventRecord(b.ev[3].get(), sh.stream));
     out.resize(n);
     HIPTRY(hipMemcpyAsync(out.data(), b.verdict.get(), n, hipMemcpyDeviceToHost, sh.stream));

@@ -1,7 +1,7 @@
 // bmpow_rx.hip -- decrypted msgs from plaintext bytes to the inputs of the signature and identification
 // kernels, and from their outputs to the final record (gfx950; include/bmpow_rx.h).
 //
-// Reference: processmsg, src/class_objectProcessor.py:441-452 and :488-591.  Host side: bmpow_host_rx.hip.
+// Reference: processmsg, src/class_objectProcessor.py:441-452 and :488-591.  Host side: bmpow_host_rx.hip, through bmpow_host_rows.h.
 //
 //   rx_walk_kernel   : one lane per row.  The field walk, the DER parse of the signature and the range
 //                      checks of r, s and the key (bmpow_rx_fmt.h, the text the host test runs), and from
@@ -21,32 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bmpow_rx_fmt.h"
+#include "bmpow_rx_dev.h"
 #include "bmpow_rx_kernels.h"
-#include "sha512_dev.h"
-
-namespace {
-
-// secp256k1's generator, little-endian limbs
-__device__ const uint32_t kGx[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu,
-                                    0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
-__device__ const uint32_t kGy[8] = {0xFB10D4B8u, 0x9C47D08Fu, 0xA6855419u, 0xFD17B448u,
-                                    0x0E1108A8u, 0x5DA4FBFCu, 0x26A3C465u, 0x483ADA77u};
-
-struct PlainSrc {  // a row's plaintext for rxf::pack_chunk
-  const uint4* chunks;  // its slot in the pool
-  uint32_t nchunks;     // of the slot, clipped to the pool
-  const uint8_t* bytes;
-  uint32_t len;
-  __device__ __forceinline__ void load16(uint32_t k, uint32_t (&w)[4]) const {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (k < nchunks) v = chunks[k];
-    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-  }
-  __device__ __forceinline__ uint32_t byte(uint32_t i) const { return i < len ? bytes[i] : 0u; }
-};
-
-}  // namespace
 
 __global__ __launch_bounds__(SG_BLOCK) void rx_walk_kernel(const rx_row* __restrict__ rows,
                                                            const uint8_t* __restrict__ plain, uint32_t n,
@@ -71,19 +47,7 @@ __global__ __launch_bounds__(SG_BLOCK) void rx_walk_kernel(const rx_row* __restr
     if (rxf::load_key(p + key_off, x, y) && (flag & RX_FLAG_DER)) flag |= RX_FLAG_REAL;
   }
   const bool real = (flag & RX_FLAG_REAL) != 0;
-  sg_sig sig;
-  ec::ge pt;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sig.r.d[i] = real ? r[i] : (i == 0 ? 1u : 0u);
-    sig.s.d[i] = real ? s[i] : (i == 0 ? 1u : 0u);
-    pt.x.d[i] = real ? x[i] : kGx[i];
-    pt.y.d[i] = real ? y[i] : kGy[i];
-  }
-  sig.blk = row->blk;
-  sig.nblk = real ? rxf::signed_blocks(rec.prefix_len, rec.bottom) : 0u;
-  sigs[o] = sig;
-  pts[o] = pt;
+  rxd::emit_sig(real, r, s, x, y, row->blk, rxf::signed_blocks(rec.prefix_len, rec.bottom), sigs[o], pts[o]);
 
   rx_pk k;
   k.plen = rxf::put_prefix(row->head, rec.claimed_stream, k.pre);
@@ -92,15 +56,7 @@ __global__ __launch_bounds__(SG_BLOCK) void rx_walk_kernel(const rx_row* __restr
 
   // the identification's input: the keys' bytes as they lie in the plaintext (the walk's 170-byte floor
   // keeps all 128 inside it); zeros for a row the walk rejected
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (walked) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) w[j >> 2] |= (uint32_t)p[key_off + 16 * q + j] << (8 * (j & 3));
-    }
-    keys[8 * (uint64_t)o + q] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  rxd::gather_keys(walked, p, key_off, keys + 8 * (uint64_t)o);
   versions[o] = rec.sender_version;
   streams[o] = rec.sender_stream;
   flags[o] = flag;
@@ -116,22 +72,9 @@ __global__ __launch_bounds__(64) void rx_pack_kernel(const rx_row* __restrict__ 
   if (o >= n) return;
   const uint32_t nblk = sigs[o].nblk;
   if (nblk == 0) return;
-  const uint64_t base = 4ull * sigs[o].blk;
   const rx_pk k = pk[o];
-  const uint64_t first = rows[o].poff >> 4;
-  PlainSrc src;
-  src.len = rows[o].plen;
-  src.chunks = plain + first;
-  const uint64_t want = ((uint64_t)src.len + 15) >> 4, room = first < plain_chunks ? plain_chunks - first : 0;
-  src.nchunks = (uint32_t)(want < room ? want : room);
-  src.bytes = reinterpret_cast<const uint8_t*>(plain) + rows[o].poff;
-  if ((uint64_t)src.nchunks * 16 < src.len) src.len = src.nchunks * 16;  // never past the pool
-#pragma unroll 1
-  for (uint32_t c = sub; c < 4 * nblk; c += RX_PACK_LANES) {
-    uint32_t w[4];
-    rxf::pack_chunk(c, nblk, k.pre, k.plen, k.bottom, src, w);
-    if (base + c < pool_chunks) pool[base + c] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  rxd::pack_row<6>(sub, RX_PACK_LANES, rows[o].poff, rows[o].plen, plain, plain_chunks, sigs[o].blk, nblk, k.pre, k.plen,
+                   k.bottom, 0u, pool, pool_chunks);
 }
 
 __global__ __launch_bounds__(SG_BLOCK) void rx_finish_kernel(const rx_row* __restrict__ rows,
@@ -162,38 +105,17 @@ __global__ __launch_bounds__(SG_BLOCK) void rx_finish_kernel(const rx_row* __res
   // sigHash: the signature parsed (good implies RX_FLAG_DER), so it is 8 .. 72 bytes of the plaintext
   const uint32_t slen = rec[18] <= rxf::kMaxDer ? rec[18] : rxf::kMaxDer;
   const uint8_t* sp = plain + rows[o].poff + rec[17];
-  uint64_t w[16], h[8];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) w[i] = 0;
-#pragma unroll
-  for (int i = 0; i <= (int)rxf::kMaxDer; ++i) {
-    const uint32_t b = (uint32_t)i < slen ? sp[(uint32_t)i < slen ? i : 0] : (uint32_t)i == slen ? 0x80u : 0u;
-    w[i >> 3] |= (uint64_t)b << (56 - 8 * (i & 7));
-  }
-  w[15] = 8ull * slen;
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {  // one compress body for both hashes
-    if (pass) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w[i] = h[i];
-      w[8] = PAD;
-#pragma unroll
-      for (int i = 9; i < 15; ++i) w[i] = 0;
-      w[15] = 64 * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = IV(i);
-    compress(h, w);
-  }
+  uint64_t h[4];
+  rxd::sig_hash(sp, slen, h);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    rec[26 + 2 * i] = __builtin_bswap32(hi32(h[4 + i]));
-    rec[27 + 2 * i] = __builtin_bswap32(lo32(h[4 + i]));
+    rec[26 + 2 * i] = __builtin_bswap32(hi32(h[i]));
+    rec[27 + 2 * i] = __builtin_bswap32(lo32(h[i]));
   }
 }
 
 // ---------------------------------------------------------------------------------------
-// Launch wrappers (C++ linkage, used by bmpow_host_rx.hip).  stride is a multiple of SG_BLOCK.
+// Launch wrappers (C++ linkage, the msg family's in bmpow_host_rx.h).  stride is a multiple of SG_BLOCK.
 // ---------------------------------------------------------------------------------------
 hipError_t rx_launch_walk(hipStream_t st, const rx_row* rows, const uint8_t* plain, uint32_t n, uint32_t stride,
                           bmpow_rx_msg_rec* recs, sg_sig* sigs, ec::ge* pts, uint4* keys, uint64_t* versions,

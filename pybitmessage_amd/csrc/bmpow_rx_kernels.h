@@ -1,5 +1,5 @@
 // bmpow_rx_kernels.h -- device data layout and launch wrappers of the msg processing (bmpow_rx.hip),
-// shared with its host unit (bmpow_host_rx.hip).
+// shared with the host units of the msg family (bmpow_host_rx.h: bmpow_host_rx.hip, bmpow_host_rxopen.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

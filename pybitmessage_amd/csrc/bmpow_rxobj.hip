@@ -24,32 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bmpow_rx_fmt.h"
+#include "bmpow_rx_dev.h"
 #include "bmpow_rxobj_kernels.h"
-#include "sha512_dev.h"
-
-namespace {
-
-// secp256k1's generator, little-endian limbs
-__device__ const uint32_t kGx[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu,
-                                    0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
-__device__ const uint32_t kGy[8] = {0xFB10D4B8u, 0x9C47D08Fu, 0xA6855419u, 0xFD17B448u,
-                                    0x0E1108A8u, 0x5DA4FBFCu, 0x26A3C465u, 0x483ADA77u};
-
-struct SourceSrc {  // a row's plaintext (or object) for rxf::pack_chunk_n
-  const uint4* chunks;  // its slot in the pool
-  uint32_t nchunks;     // of the slot, clipped to the pool
-  const uint8_t* bytes;
-  uint32_t len;
-  __device__ __forceinline__ void load16(uint32_t k, uint32_t (&w)[4]) const {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (k < nchunks) v = chunks[k];
-    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-  }
-  __device__ __forceinline__ uint32_t byte(uint32_t i) const { return i < len ? bytes[i] : 0u; }
-};
-
-}  // namespace
 
 __global__ __launch_bounds__(SG_BLOCK) void rxo_walk_kernel(const rxo_row* __restrict__ rows,
                                                             const uint8_t* __restrict__ plain, uint32_t n,
@@ -74,19 +50,7 @@ __global__ __launch_bounds__(SG_BLOCK) void rxo_walk_kernel(const rxo_row* __res
     if (rxf::load_key(p + w.key_off, x, y) && (flag & RXO_FLAG_DER)) flag |= RXO_FLAG_REAL;
   }
   const bool real = (flag & RXO_FLAG_REAL) != 0;
-  sg_sig sig;
-  ec::ge pt;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sig.r.d[i] = real ? r[i] : (i == 0 ? 1u : 0u);
-    sig.s.d[i] = real ? s[i] : (i == 0 ? 1u : 0u);
-    pt.x.d[i] = real ? x[i] : kGx[i];
-    pt.y.d[i] = real ? y[i] : kGy[i];
-  }
-  sig.blk = row->blk;
-  sig.nblk = real ? rxf::signed_blocks(rec.prefix_len, rec.bottom) : 0u;
-  sigs[o] = sig;
-  pts[o] = pt;
+  rxd::emit_sig(real, r, s, x, y, row->blk, rxf::signed_blocks(rec.prefix_len, rec.bottom), sigs[o], pts[o]);
 
   rxo_pk k;
   rxf::put_prefix_obj(row->head, rec.payload_off <= hlen ? rec.payload_off : hlen, k.pre);
@@ -97,15 +61,7 @@ __global__ __launch_bounds__(SG_BLOCK) void rxo_walk_kernel(const rxo_row* __res
   pk[o] = k;
 
   // the identification's input: the keys' bytes as they lie in the source (w.keys: all 128 inside it)
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    uint32_t v[4] = {0, 0, 0, 0};
-    if (w.keys) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j >> 2] |= (uint32_t)p[w.key_off + 16 * q + j] << (8 * (j & 3));
-    }
-    keys[8 * (uint64_t)o + q] = make_uint4(v[0], v[1], v[2], v[3]);
-  }
+  rxd::gather_keys(w.keys, p, w.key_off, keys + 8 * (uint64_t)o);
   versions[o] = rec.sender_version;
   streams[o] = rec.sender_stream;
   flags[o] = flag;
@@ -135,22 +91,9 @@ __global__ __launch_bounds__(64) void rxo_pack_kernel(const rxo_row* __restrict_
   if (o >= n) return;
   const uint32_t nblk = sigs[o].nblk;
   if (nblk == 0) return;
-  const uint64_t base = 4ull * sigs[o].blk;
   const rxo_pk k = pk[o];
-  const uint64_t first = rows[o].poff >> 4;
-  SourceSrc src;
-  src.len = rows[o].plen;
-  src.chunks = plain + first;
-  const uint64_t want = ((uint64_t)src.len + 15) >> 4, room = first < plain_chunks ? plain_chunks - first : 0;
-  src.nchunks = (uint32_t)(want < room ? want : room);
-  src.bytes = reinterpret_cast<const uint8_t*>(plain) + rows[o].poff;
-  if ((uint64_t)src.nchunks * 16 < src.len) src.len = src.nchunks * 16;  // never past the pool
-#pragma unroll 1
-  for (uint32_t c = sub; c < 4 * nblk; c += RXO_PACK_LANES) {
-    uint32_t w[4];
-    rxf::pack_chunk_n<(int)rxf::kObjPrefixWords>(c, nblk, k.pre, k.plen, k.bottom, k.skip, src, w);
-    if (base + c < pool_chunks) pool[base + c] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  rxd::pack_row<(int)rxf::kObjPrefixWords>(sub, RXO_PACK_LANES, rows[o].poff, rows[o].plen, plain, plain_chunks,
+                                           sigs[o].blk, nblk, k.pre, k.plen, k.bottom, k.skip, pool, pool_chunks);
 }
 
 __global__ __launch_bounds__(SG_BLOCK) void rxo_finish_kernel(const rxo_row* __restrict__ rows,
@@ -209,32 +152,11 @@ __global__ __launch_bounds__(SG_BLOCK) void rxo_finish_kernel(const rxo_row* __r
   const uint32_t soff = (uint64_t)rec->sig_off + slen <= row->plen ? rec->sig_off : 0u;
   const uint8_t* sp = plain + row->poff + soff;
   const uint32_t have = (uint64_t)soff + slen <= row->plen ? slen : 0u;
-  uint64_t w[16], h[8];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) w[i] = 0;
-#pragma unroll
-  for (int i = 0; i <= (int)rxf::kMaxDer; ++i) {
-    const uint32_t b = (uint32_t)i < have ? sp[(uint32_t)i < have ? i : 0] : (uint32_t)i == have ? 0x80u : 0u;
-    w[i >> 3] |= (uint64_t)b << (56 - 8 * (i & 7));
-  }
-  w[15] = 8ull * have;
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {  // one compress body for both hashes
-    if (pass) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w[i] = h[i];
-      w[8] = PAD;
-#pragma unroll
-      for (int i = 9; i < 15; ++i) w[i] = 0;
-      w[15] = 64 * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = IV(i);
-    compress(h, w);
-  }
+  uint64_t h[4];
+  rxd::sig_hash(sp, have, h);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const uint32_t hi = hi32(h[4 + i]), lo = lo32(h[4 + i]);
+    const uint32_t hi = hi32(h[i]), lo = lo32(h[i]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       rec->sig_hash[8 * i + j] = (uint8_t)(hi >> (24 - 8 * j));
@@ -244,7 +166,7 @@ __global__ __launch_bounds__(SG_BLOCK) void rxo_finish_kernel(const rxo_row* __r
 }
 
 // ---------------------------------------------------------------------------------------
-// Launch wrappers (C++ linkage, used by bmpow_host_rxobj.hip).  stride is a multiple of SG_BLOCK.
+// Launch wrappers (C++ linkage, the object family's in bmpow_host_rxobj.hip).  stride is a multiple of SG_BLOCK.
 // ---------------------------------------------------------------------------------------
 hipError_t rxo_launch_walk(hipStream_t st, const rxo_row* rows, const uint8_t* plain, uint32_t n, uint32_t stride,
                            bmpow_rx_obj_rec* recs, sg_sig* sigs, ec::ge* pts, uint4* keys, uint64_t* versions,

@@ -17,16 +17,16 @@
 #include "bmpow_rxopen_kernels.h"
 #include "bmpow_rxopen_rows.h"
 
-__global__ __launch_bounds__(RXO_BLOCK) void rxo_open_kernel(const rxo_row* __restrict__ orows,
+__global__ __launch_bounds__(RXS_BLOCK) void rxs_open_kernel(const rxs_row* __restrict__ orows,
                                                              const uint64_t* __restrict__ key_e, uint32_t n_src,
                                                              const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain,
                                                              uint64_t plain_bytes, uint32_t n, int32_t* __restrict__ opened) {
   __shared__ aes::DecTab tab;
-  aes::fill_dec(tab, threadIdx.x, RXO_BLOCK);
+  aes::fill_dec(tab, threadIdx.x, RXS_BLOCK);
   __syncthreads();
-  const uint32_t o = blockIdx.x * RXO_BLOCK + threadIdx.x;
+  const uint32_t o = blockIdx.x * RXS_BLOCK + threadIdx.x;
   if (o >= n) return;
-  const rxo_row r = orows[o];
+  const rxs_row r = orows[o];
   const uint64_t poff = rows[o].poff, at = 64ull * r.blk;
   // the padded pool row ends behind the ciphertext (bmpow_rxopen_rows.h); the slot holds clen bytes
   const bool fits = r.src < n_src && r.clen >= 16 && r.clen % 16 == 0 && r.body_off >= 16 && at + r.body_off + r.clen + 9 <= pool_bytes &&
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(RXO_BLOCK) void rxo_open_kernel(const rxo_row* __re
   const uint4 iv = *reinterpret_cast<const uint4*>(pool + at);
   ivw[0] = __builtin_bswap32(iv.x), ivw[1] = __builtin_bswap32(iv.y), ivw[2] = __builtin_bswap32(iv.z),
   ivw[3] = __builtin_bswap32(iv.w);
-  const int32_t got = rxo::open_row(pool + at + r.body_off, r.clen, key, ivw, plain + poff, tab);
+  const int32_t got = rxs::open_row(pool + at + r.body_off, r.clen, key, ivw, plain + poff, tab);
   rows[o].plen = got < 0 ? 0u : (uint32_t)got;
   opened[o] = got;
 }
@@ -53,12 +53,12 @@ __global__ __launch_bounds__(RXO_BLOCK) void rxo_open_kernel(const rxo_row* __re
 // ---------------------------------------------------------------------------------------
 // Launch wrapper (C++ linkage).
 // ---------------------------------------------------------------------------------------
-hipError_t rxo_launch_open(hipStream_t st, const rxo_row* orows, const uint64_t* key_e, uint32_t n_src,
+hipError_t rxs_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t* key_e, uint32_t n_src,
                            const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain, uint64_t plain_bytes, uint32_t n,
                            int32_t* opened) {
   if (n == 0) return hipSuccess;
   if (!orows || !key_e || !pool || !rows || !plain || !opened) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rxo_open_kernel, dim3((n + RXO_BLOCK - 1) / RXO_BLOCK), dim3(RXO_BLOCK), 0, st, orows, key_e, n_src,
+  hipLaunchKernelGGL(rxs_open_kernel, dim3((n + RXS_BLOCK - 1) / RXS_BLOCK), dim3(RXS_BLOCK), 0, st, orows, key_e, n_src,
                      pool, pool_bytes, rows, plain, plain_bytes, n, opened);
   return hipGetLastError();
 }

@@ -23,7 +23,7 @@
 #include "aes256_dev.h"
 #include "bmpow_seal_rows.h"  // sl::store16
 
-namespace rxo {
+namespace rxs {
 
 BM_DEV void load_chunk(uint32_t (&w)[4], const uint8_t* p) {  // 16-byte aligned; words in memory order
   __builtin_memcpy(w, __builtin_assume_aligned(p, 16), 16);
@@ -95,4 +95,4 @@ BM_DEV int32_t open_row(const uint8_t* src, uint32_t clen, const uint32_t (&key)
   return (int32_t)(clen - pad);
 }
 
-}  // namespace rxo
+}  // namespace rxs

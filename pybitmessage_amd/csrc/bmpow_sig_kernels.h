@@ -1,5 +1,6 @@
 // bmpow_sig_kernels.h -- device data layout and launch wrappers of the signature verification
-// (bmpow_sig.hip), shared with its host unit (bmpow_host_sig.hip).
+// (bmpow_sig.hip), shared with the host units that launch them (bmpow_host_sig.hip; bmpow_host_rows.h for
+// the receive side's rows) and with the kernels that write their inputs (bmpow_rx_dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -101,12 +101,12 @@ static void open_once(const std::vector<uint8_t>& ct, uint32_t body_off, const u
   const int32_t want_len = want ? (int32_t)want->size() : -1;
 
   Heap slot(16, clen);
-  const int32_t got = rxo::open_row(row.p + body_off, clen, k, ivw, slot.p, g_dec);
+  const int32_t got = rxs::open_row(row.p + body_off, clen, k, ivw, slot.p, g_dec);
   CHECK(got == want_len, "%s: length %d, want %d (body_off %u, clen %u)", what, got, want_len, body_off, clen);
   CHECK(std::memcmp(slot.p, expect.data(), clen) == 0, "%s: slot bytes (body_off %u, clen %u)", what, body_off, clen);
 
   Heap guarded(16, (size_t)clen + 32);  // sentinel | slot | sentinel
-  const int32_t again = rxo::open_row(row.p + body_off, clen, k, ivw, guarded.p + 16, g_dec);
+  const int32_t again = rxs::open_row(row.p + body_off, clen, k, ivw, guarded.p + 16, g_dec);
   CHECK(again == want_len, "%s: length %d the second time", what, again);
   CHECK(std::memcmp(guarded.p + 16, expect.data(), clen) == 0, "%s: guarded slot bytes", what);
   for (int i = 0; i < 16; ++i)

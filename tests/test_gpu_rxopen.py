@@ -13,12 +13,13 @@ import pytest
 from tests.conftest import load_golden
 from tests.test_gpu_rx import compose, row
 from tests.test_rx import LINE_STATUS, check_row_against_fixture
+from tests.test_rxobj import BROADCAST
 
 pytestmark = pytest.mark.gpu
 
 SET = 1 << 18  # objects of one ECIES set
 TAIL = len(b'encrypted payload')  # what compose() puts where the payload goes
-ROW_UP, ROW_DOWN = 80 + 16, 208 + 4  # a matched row's descriptors (rx_row, rxo_row); its record and opened[]
+ROW_UP, ROW_DOWN = 80 + 16, 208 + 4  # a matched row's descriptors (rx_row, rxs_row); its record and opened[]
 
 
 @pytest.fixture(scope='module')
@@ -117,6 +118,29 @@ def assert_equals_composition(objs, ripes, privs):
     return got
 
 
+def check_msg_result(m, res, i):
+    """Row i of a msg batch against the fixture's final record, digest and result."""
+    check_row_against_fixture(m, res, i, final=True)
+    assert int(res.digest[i]) == m['digest'], m['name']
+    if m['result'] is not None:
+        got = {'fromAddress': res.fromAddress(i), 'ripe': res.ripe(i).hex(), 'sigHash': res.sigHash(i).hex()}
+        assert got == m['result'], m['name']
+    else:
+        assert res.recs[i]['ripe'].tobytes() == bytes(20) and res.recs[i]['sig_hash'].tobytes() == bytes(32)
+
+
+def check_sealed_row(m, res, i):
+    """Row i of open_sealed_msgs against the fixture: the record, and whose key opened it to what."""
+    if m['line'] in (444, 478):
+        check_row_against_fixture(m, res, i, final=True)
+        assert int(res.digest[i]) == m['digest'], m['name']
+        assert int(res.status[i]) == LINE_STATUS[m['line']] and int(res.match[i]) == -1, m['name']
+        assert res.toRipe(i) is None and res.plaintexts[i] == b''
+        return
+    assert res.toRipe(i).hex() == m['toRipe'] and res.plaintexts[i].hex() == m['plaintext'], m['name']
+    check_msg_result(m, res, i)
+
+
 # ------------------------------------------------------------------ 1. the fixture
 def test_fixture_in_one_call(gpulib, kats):
     from pybitmessage_amd import receive
@@ -125,18 +149,7 @@ def test_fixture_in_one_call(gpulib, kats):
     res = receive.open_sealed_msgs(objs, keys)
     assert len(res) == len(objs)
     for i, m in enumerate(kats['msgs']):
-        check_row_against_fixture(m, res, i, final=True)
-        assert int(res.digest[i]) == m['digest'], m['name']
-        if m['line'] in (444, 478):
-            assert int(res.status[i]) == LINE_STATUS[m['line']] and int(res.match[i]) == -1, m['name']
-            assert res.toRipe(i) is None and res.plaintexts[i] == b''
-            continue
-        assert res.toRipe(i).hex() == m['toRipe'] and res.plaintexts[i].hex() == m['plaintext'], m['name']
-        if m['result'] is not None:
-            got = {'fromAddress': res.fromAddress(i), 'ripe': res.ripe(i).hex(), 'sigHash': res.sigHash(i).hex()}
-            assert got == m['result'], m['name']
-        else:
-            assert res.recs[i]['ripe'].tobytes() == bytes(20) and res.recs[i]['sig_hash'].tobytes() == bytes(32)
+        check_sealed_row(m, res, i)
     assert [m['name'] for m, s in zip(kats['msgs'], res.status) if s == receive.NOT_MINE] == ['not_mine']
     assert res.accepted() == [i for i, m in enumerate(kats['msgs']) if m['line'] is None]
     assert receive.process_sealed_msgs(objs, keys) == receive.process_msgs(objs, keys)
@@ -423,3 +436,68 @@ def test_byte_counters(gpulib, user, handful):
     # ciphertext's length) -- not a byte for a row that did not match
     assert st['bytes_down'] == 4 * len(tried) + 18 * ROW_DOWN + sum(opened)
     assert sum(len(got.plaintexts[i]) for i in range(len(objs))) < sum(opened) <= sum(len(p) for p, o in zip(tried, objs) if o in mine)
+
+
+# ------------------------------------------------------------------ 10. the four receive-side calls, alternating
+def test_four_entry_points_alternate_in_one_process(gpulib, kats):
+    """bmpow_rx_objects, bmpow_rx_sealed_msgs, bmpow_rx_msgs and bmpow_sig_verify share one set planner, one
+    verification chain and one rows driver, and the object rows (120 bytes) and the opening kernel's rows
+    (16 bytes) are two types in one library.  Here they take turns in one process, every call growing its own
+    buffers afresh, at 1, 65 and 129 rows -- stride above n each time, the larger two across a wave and an
+    SG_BLOCK boundary -- over the golden fixtures tiled to that size; every row of every call is its
+    fixture's."""
+    from pybitmessage_amd import receive, signatures
+    from tests.test_rxobj import check_row_against_fixture as check_obj_row, device_rows
+
+    def tile(rows, first, n):  # n rows from rows[first] on, round and round
+        return [rows[(first + k) % len(rows)] for k in range(n)]
+
+    obj_rows = device_rows(load_golden('rxobj_kats.json'))
+    obj_first = next(i for i, r in enumerate(obj_rows) if r[1]['result'] is not None)
+    msgs = kats['msgs']
+    msg_first = next(i for i, m in enumerate(msgs) if m['name'] == 'ok_v4')
+    opened = [m for m in msgs if m['line'] != 478]  # bmpow_rx_msgs takes the rows some key decrypts
+    opened_first = next(i for i, m in enumerate(opened) if m['name'] == 'ok_v4')
+    keys = {bytes.fromhex(k['ripe']): bytes.fromhex(k['privkey']) for k in kats['recipients']}
+    sig_kats = load_golden('sig_kats.json')
+    sigs = [(k['name'], bytes.fromhex(k['msg']), bytes.fromhex(k['sig']), bytes.fromhex(k['key']), k['code'])
+            for k in sig_kats['cases']]
+    sig_first = next(i for i, c in enumerate(sigs) if c[4] == 2)
+
+    for n in (1, 65, 129):
+        receive.obj_reset_stats(), receive.sealed_reset_stats(), receive.reset_stats()
+        rows = tile(obj_rows, obj_first, n)
+        res = receive.open_objects([r[0] for r in rows], [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows])
+        assert len(res) == n
+        for i, (kind, e, _obj, _plain, _expect) in enumerate(rows):
+            check_obj_row(kind, e, res, i, final=True)
+            assert int(res.recs[i]['digest']) == e['digest'], (n, e['name'])
+            if e['result'] is not None:
+                assert (res.fromAddress(i), res.ripe(i).hex()) == (e['result']['fromAddress'], e['result']['ripe']), (n, e['name'])
+                if kind == BROADCAST:
+                    assert res.sigHash(i).hex() == e['result']['sigHash'], (n, e['name'])
+                else:
+                    assert res.storedData(i).hex() == e['result']['storedData'] and res.sigHash(i) == bytes(32), (n, e['name'])
+
+        rows = tile(msgs, msg_first, n)
+        res = receive.open_sealed_msgs([bytes.fromhex(m['obj']) for m in rows], keys)
+        assert len(res) == n
+        for i, m in enumerate(rows):
+            check_sealed_row(m, res, i)
+
+        rows = tile(opened, opened_first, n)
+        res = receive.open_msgs([bytes.fromhex(m['obj']) for m in rows], [bytes.fromhex(m['plaintext']) for m in rows],
+                                [bytes.fromhex(m['toRipe']) for m in rows])
+        assert len(res) == n
+        for i, m in enumerate(rows):
+            check_msg_result(m, res, i)
+
+        rows = tile(sigs, sig_first, n)
+        got = signatures.verify_batch_digest([c[1] for c in rows], [c[2] for c in rows], [c[3] for c in rows])
+        assert [(c[0], c[4], g) for c, g in zip(rows, got) if c[4] != g] == [], n
+
+        # one set each, of the family's nine launches (ten behind the opening kernel, four in front for one key group)
+        assert (receive.obj_stats()['sets'], receive.obj_stats()['launches']) == (1, 9), n
+        assert (receive.stats()['sets'], receive.stats()['launches']) == (1, 9), n
+        st = receive.sealed_stats()
+        assert (st['sets'], st['rx_launches']) == (1, 10) and st['matched'] > 0, n

@@ -62,3 +62,22 @@ def test_owner_unit_under_sanitizer():
     assert r.returncode == 0, r.stderr[-4000:]
     assert 'all owner checks passed' in r.stderr
     assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+
+
+def test_set_planner_under_sanitizer():
+    """The set planner the receive-side host units share (pybitmessage_amd/csrc/bmpow_set_plan.h) at tiny
+    limits (tests/native/setplan_sim.cpp): the boundary cases the library itself only meets at 2^18 rows or
+    256 MB, and 1,000 seeded random lists against a naive restatement.  A stand-alone program under
+    AddressSanitizer + UBSan that loads neither HIP nor the library."""
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, 'setplan_sim_asan_ubsan')
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Werror'] + FLAVOURS['asan_ubsan'] +
+                          ['-I', os.path.join(ROOT, 'pybitmessage_amd', 'csrc'),
+                           os.path.join(ROOT, 'tests', 'native', 'setplan_sim.cpp'), '-o', exe])
+    env = dict(os.environ)
+    env['ASAN_OPTIONS'] = 'halt_on_error=1 detect_leaks=1'
+    env['UBSAN_OPTIONS'] = 'halt_on_error=1 print_stacktrace=1'
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert 'all set planner checks passed' in r.stderr
+    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr

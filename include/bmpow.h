@@ -105,7 +105,10 @@ BMPOW_API const char *bmpow_version(void);
 /* ---- interrupt (replaces the dead OpenCL shutdown check, src/openclpow.py:10,99) ---- */
 
 /* Async-signal-safe.  In-flight and later searches return BMPOW_E_ABORTED at their next
- * step boundary (<= one launch, ~tens of ms) until bmpow_clear_abort(). */
+ * step boundary (<= one launch, ~tens of ms) until bmpow_clear_abort().  The flag is the process's:
+ * every other call that launches on a device (receive-side verification, bmpow_pubkeys, the address
+ * search and the units of the other headers) returns BMPOW_E_ABORTED too while it is set, when it
+ * starts or at its next set of rows. */
 BMPOW_API void bmpow_abort(void);
 BMPOW_API void bmpow_clear_abort(void);
 

@@ -9,7 +9,8 @@
  * shard computing both hash chains per object, and the header walk and checks on host threads.
  *
  * Same conventions as bmpow.h (return codes, bmpow_last_error, thread safety).  The batch calls are
- * sharded over every selected shard, as bmpow_verify_batch is.
+ * sharded over every selected shard, as bmpow_verify_batch is, and like it return BMPOW_E_ABORTED
+ * while bmpow_abort()'s flag is set.
  */
 #ifndef BMPOW_INTAKE_H
 #define BMPOW_INTAKE_H

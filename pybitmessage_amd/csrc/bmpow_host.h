@@ -157,6 +157,10 @@ struct Shard {
 };
 
 inline std::vector<Shard> g_shards;
+// Counts the shard sets: bumped whenever g_shards is released (select_devices, shutdown).  A batch, a
+// verification batch or a service's session remembers the set its device buffers were made for and is
+// refused (BMPOW_E_STATE) under any other -- a re-selection to a set of the same size included.  Under g_mu.
+inline uint64_t g_generation = 0;
 // The cross-shard bound (bmpow_layout.h): BM_MAX_SHARDS rows of BM_XSLOTS words, host-pinned, coherent
 // and mapped into every device; allocated with the shard set.
 inline PinBuf<unsigned long long> g_xb;

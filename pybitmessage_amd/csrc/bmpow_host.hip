@@ -116,6 +116,7 @@ void apply_engine_groups() {
 }
 
 int select_devices(const std::vector<int>& ids) {
+  ++g_generation;  // whatever was built for the old set is stale, whether or not the new one is as large
   g_engine.reset();  // joins the steppers once their launches are applied
   free_one();
   free_shards();
@@ -287,6 +288,7 @@ static void shutdown_locked() {
     drop_scratch(el);
     g_engine->detach(el);
   }
+  ++g_generation;
   g_engine.reset();
   free_one();
   free_shards();

@@ -244,6 +244,7 @@ int bmpow_pubkeys(size_t n, const uint8_t* privkeys, uint8_t* pubkeys_out) {
   if (n == 0) return 0;
   if (!privkeys || !pubkeys_out) return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffULL) return set_err(BMPOW_E_ARG, "too many keys");
+  if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
   Shard& sh = g_shards[0];
   rc = ensure_table(sh, 0);
   if (rc < 0) return rc;

@@ -172,6 +172,7 @@ struct bmpow_batch : bmsched::BatchState {
     bmown::DevBuf<uint64_t> d_vpool;           // copy of vpool (var-form objects' words), vcap words
   };
   std::vector<Dev> dev;  // one per shard (indexed like g_shards)
+  uint64_t generation = ~0ULL;  // g_generation of the shard set dev[] was uploaded to (batch_upload)
   size_t vcap = 0;         // words allocated per shard for the var pool
   size_t vsynced = 0;      // vpool words already on the devices (of epoch vepoch)
   uint64_t vepoch = ~0ULL;
@@ -229,6 +230,7 @@ int sync_vpool(std::unique_lock<std::mutex>& lk, bmpow_batch* b) {
 int batch_upload(std::unique_lock<std::mutex>& lk, bmpow_batch* b) {
   b->dev.clear();
   b->dev.resize(g_shards.size());
+  b->generation = g_generation;
   const size_t n = std::max<size_t>(b->cap, std::max<size_t>(b->n, 1));
   b->cap = n;
   for (size_t s = 0; s < g_shards.size(); ++s) {
@@ -298,7 +300,7 @@ int init_slots(bmpow_batch* b, const uint32_t* slots, size_t m) {
 int batch_add_locked(std::unique_lock<std::mutex>& lk, bmpow_batch* b, size_t m, const uint8_t* ihs,
                      const uint64_t* targets, const uint64_t* start, uint32_t* slot_out,
                      const uint64_t* ih_off = nullptr) {
-  if (b->dev.size() != g_shards.size()) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
+  if (b->generation != g_generation) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
   const size_t fresh = m > b->free_slots.size() ? m - b->free_slots.size() : 0;
   if (b->n + fresh > 0xffffffffULL) return set_err(BMPOW_E_ARG, "too many objects");
   if (b->n + fresh > b->cap) quiesce(lk, b);  // the tables will be reallocated
@@ -619,7 +621,7 @@ bmsched::ServiceOps service_ops(bmpow_service* s) {
   ops.add = [s](size_t n, const uint8_t* ihs, const uint64_t* ih_off, const uint64_t* tg, uint32_t* slots,
                 std::string& err) {
     std::lock_guard<FairMutex> g(g_mu);
-    if (!g_engine || s->b->dev.size() != g_shards.size()) return engine_gone(err);
+    if (!g_engine || s->b->generation != g_generation) return engine_gone(err);
     std::unique_lock<std::mutex> lk(g_engine->mu);
     const int rc = batch_add_locked(lk, s->b, n, ihs, tg, nullptr, slots, ih_off);
     if (rc < 0) err = g_err;
@@ -629,7 +631,7 @@ bmsched::ServiceOps service_ops(bmpow_service* s) {
   // as an object finished, so the service hands it out while the devices go on
   ops.step = [s](std::string& err) {
     std::lock_guard<FairMutex> g(g_mu);
-    if (!g_engine || s->b->dev.size() != g_shards.size()) return engine_gone(err);
+    if (!g_engine || s->b->generation != g_generation) return engine_gone(err);
     std::unique_lock<std::mutex> lk(g_engine->mu);
     g_engine->attach(lk, s->b);
     bmpow_batch* b = s->b;
@@ -845,7 +847,7 @@ int bmpow_batch_step(bmpow_batch* b, uint64_t budget) {
   std::lock_guard<FairMutex> g(g_mu);
   if (!b) return set_err(BMPOW_E_STATE, "null batch");
   if (!g_engine) return set_err(BMPOW_E_STATE, "library not initialised");
-  if (b->dev.size() != g_shards.size()) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
+  if (b->generation != g_generation) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
   if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
   std::unique_lock<std::mutex> lk(g_engine->mu);
   g_engine->attach(lk, b);
@@ -874,7 +876,7 @@ int bmpow_batch_results(const bmpow_batch* b, uint64_t* nonce_out, uint64_t* tri
 int bmpow_batch_reset(bmpow_batch* b, const uint64_t* start) {
   std::lock_guard<FairMutex> g(g_mu);
   if (!b) return set_err(BMPOW_E_STATE, "null batch");
-  if (b->dev.size() != g_shards.size() || !g_engine) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
+  if (b->generation != g_generation || !g_engine) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
   std::unique_lock<std::mutex> lk(g_engine->mu);
   quiesce(lk, b);
   bmsched::reset(*b, start);

@@ -35,6 +35,7 @@ static double ms_between(clk::time_point a, clk::time_point b) {
 template <class InvOf>
 int intake_run_locked(const std::vector<Span>& spans, InvOf&& inv_of, uint64_t* pow_out) {
   if (spans.empty()) return 0;
+  if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");  // process-wide, as for every other device call
   for (const Span& s : spans)
     if (s.len > 0xffffff00ULL) return set_err(BMPOW_E_ARG, "object of 4 GiB or more");
   const clk::time_point t0 = clk::now();

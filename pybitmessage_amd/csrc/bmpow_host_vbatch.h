@@ -33,6 +33,7 @@ struct bmpow_vbatch {
   };
   std::vector<Part> parts;
   uint64_t blocks = 0;
+  uint64_t generation = ~0ULL;  // g_generation of the shard set the parts were built for (vbatch_build)
 };
 
 namespace bmhost {

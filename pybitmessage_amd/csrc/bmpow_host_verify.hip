@@ -111,6 +111,7 @@ void vbatch_release_plan(bmpow_vbatch* vb) {
 
 int vbatch_build(bmpow_vbatch* vb, const std::vector<Span>& objs, bool transient) {
   vb->n = objs.size();
+  vb->generation = g_generation;
   // the plan's vectors live in g_vplan between calls (swapped into the parts here, back by
   // vbatch_release_plan): a flood's descriptors are tens of MB, and fresh pages cost more than
   // the planning
@@ -153,6 +154,7 @@ int vbatch_build(bmpow_vbatch* vb, const std::vector<Span>& objs, bool transient
 }
 
 int vbatch_run_locked(bmpow_vbatch* vb, uint64_t* pow_out) {
+  if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");  // process-wide, as for every other device call
   for (auto& pt : vb->parts) {
     Shard& sh = g_shards[pt.shard];
     HIPTRY(hipSetDevice(sh.dev));
@@ -217,8 +219,7 @@ bmpow_vbatch* bmpow_vbatch_create(size_t n, const uint8_t* objs, const uint64_t*
 int bmpow_vbatch_run(bmpow_vbatch* vb, uint64_t* pow_out) {
   std::lock_guard<FairMutex> lk(g_mu);
   if (!vb) return set_err(BMPOW_E_STATE, "null verification batch");
-  for (auto& pt : vb->parts)
-    if (pt.shard >= g_shards.size()) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
+  if (vb->generation != g_generation) return set_err(BMPOW_E_STATE, "device set changed under a live batch");
   return vbatch_run_locked(vb, pow_out);
 }
 

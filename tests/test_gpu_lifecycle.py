@@ -2,7 +2,14 @@
 staging, run()'s rings, the verification pool and staging chunks, the address search's comb table) is
 released and rebuilt by each bmpow_set_devices, with right answers in every layout and no device
 memory left behind.  Small leaks are the native owner test's job (tests/native/own_sim.cpp); a comb
-table (64 MiB) or a verification staging chunk's pool left behind shows here.  Run on an MI355X."""
+table (64 MiB) or a verification staging chunk's pool left behind shows here.
+
+The first test re-runs PoW, the probe, the verification and the address search in each layout.  The second
+runs every crypto entry point (tests/workloads.py: the signature, send and outgoing units read the comb table
+the address search builds, the others keep grow-only buffers per call family) in each layout of a cycle run
+three times.  The third re-selects the devices under a live PowService: what the service holds was built for
+the old shard set, and the library must refuse to step it (the set's generation, not its size, decides).
+Run on an MI355X."""
 import ctypes
 import hashlib
 import random
@@ -10,7 +17,8 @@ import random
 import pytest
 
 from oracle import oracle
-from pybitmessage_amd import addressgen, proofofwork, targets, verify
+from pybitmessage_amd import _lib, addressgen, proofofwork, targets, verify, worker
+from tests import workloads
 from tests.test_addressgen import SAMPLE_DET_RIPE, SAMPLE_SEED
 
 pytestmark = pytest.mark.gpu
@@ -70,3 +78,57 @@ def test_reselecting_devices_releases_every_subsystem(gpulib, shards, golden, mo
     print('free MiB after each re-selection: %s; drop from the second to the fourth: %.1f MiB (bound %.1f)'
           % ([round(f / MIB, 1) for f in free], drop / MIB, BOUND / MIB))
     assert drop <= BOUND
+
+
+# Pass 3 against pass 2, position by position: 32 MiB is half the smallest persistent thing this test exists
+# to catch -- the 16-bit comb table (64 MiB), which four subsystems now read, or a 64 MiB pool.  Not a measured
+# number.  Pass 1 sets the HIP runtime's high-water marks (streams, staging, code objects) and is not compared.
+CYCLE_BOUND = 32 * MIB
+
+
+def test_reselecting_devices_with_every_workload_leaves_no_device_memory(gpulib, shards):
+    workloads.baseline()  # in the default layout, before the first re-selection
+    free = []
+    for _ in range(3):
+        for layout in LAYOUTS:
+            shards(layout)
+            free.append(device_free_bytes())
+            assert workloads.round_equals_baseline() == [], layout
+    n = len(LAYOUTS)
+    drops = [a - b for a, b in zip(free[n:2 * n], free[2 * n:])]
+    print('free MiB after each re-selection, three passes over %s: %s; pass 2 -> pass 3 drops %s MiB (bound %d)'
+          % (list(LAYOUTS), [round(f / MIB, 1) for f in free], [round(d / MIB, 1) for d in drops], CYCLE_BOUND // MIB))
+    assert max(drops) <= CYCLE_BOUND
+
+
+@pytest.mark.parametrize('how', ['set_devices', 'resetPoW'])
+def test_reselection_under_a_live_service_is_refused_not_stepped(gpulib, shards, coracle, how):
+    """A PowService with an object that can never finish (target 0) and one of about 2 * 10^5 expected trials;
+    then the same layout selected again (bmpow_set_devices), or the library shut down and initialised again
+    (resetPoW).  The shard set has as many shards as before, so a comparison of sizes lets the service step
+    on the new shards with the buffers of the old ones -- silently on one device.  What must happen: the
+    object that cannot finish fails with E_STATE (the only other acceptable outcome, an exact answer from a
+    rebuilt session, does not exist for it); the small one fails the same way, unless it was answered --
+    exactly -- before the re-selection took the lock; a new object is then answered exactly; stop() returns."""
+    u64 = (1 << 64) - 1
+    shards([0])
+    rng = random.Random(4242)
+    small = (u64 // 200000, rng.randbytes(64))
+    fresh = (u64 // 200000, rng.randbytes(64))
+    svc = worker.PowService().start()
+    try:
+        ballast, pending = svc.submit_many([(0, rng.randbytes(64)), small])
+        if how == 'set_devices':
+            shards([0])
+        else:
+            assert proofofwork.resetPoW() >= 1
+        failed = ballast.exception(timeout=60)
+        assert isinstance(failed, _lib.BmpowError) and failed.code == _lib.E_STATE, failed
+        failed = pending.exception(timeout=60)
+        if failed is None:
+            assert list(pending.result(1)) == list(coracle.search(small[1], small[0]))
+        else:
+            assert isinstance(failed, _lib.BmpowError) and failed.code == _lib.E_STATE, failed
+        assert list(svc.submit(*fresh).result(60)) == list(coracle.search(fresh[1], fresh[0]))
+    finally:
+        svc.stop(30)

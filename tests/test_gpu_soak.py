@@ -10,14 +10,20 @@ layout changing between phases -- the way a long-running node uses the library.
 * one thread verifies batches of received objects (isProofOfWorkSufficient_batch, the receive side,
   protocol.py:258-286): objects given a valid nonce by run_batch at the network difficulty, the same
   with one payload byte changed, and objects with random nonces, each verdict against targets.py's
-  per-object restatement.
+  per-object restatement;
+* one thread cycles through the crypto entry points (tests/workloads.py: intake.check_objects, the POW values,
+  signatures.verify_batch_digest, ecies.decrypt_batch and aes_cbc_batch, addresses.derive_batch, the
+  receive.open_* calls, sender.sign_batch / encrypt_batch, outgoing.build_objects, the address search and
+  addressgen.pubkeys), each result byte-equal to its idle baseline, which workloads.baseline() holds against
+  the reference-made fixtures -- their call-scoped device buffers are allocated and freed on shard 0's
+  stream while the engine launches on it.
 
 Phases, run three times over: one shard; two shards sharing the device (objects nonce-sharded between them,
 cross-shard bound slots in use); three forced run() pieces on CU slices; four shards.  Every answer is
 re-hashed (trial <= target) and, while the checkers keep up, proven minimal with the C oracle
 (oracle/); the rest is counted as checked for validity only.  The process's resident memory at the end
 of each phase of the third pass is compared with the same phase of the second (after gc and
-malloc_trim): a leak per call or per layout change shows there, while what a layout holds (its streams,
+malloc_trim): a leak per call or per layout change -- of the crypto calls' buffers too -- shows there, while what a layout holds (its streams,
 rings and staging buffers) and the HIP runtime's high-water marks, set in the first pass, do not
 (tools/diag/rss_layout.py).
 """
@@ -32,6 +38,7 @@ import time
 
 import pytest
 
+from tests import workloads
 from tests.test_gpu_engine import run_split  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +67,7 @@ def _object(rng):
 
 def test_soak_every_entry_point_at_once(gpulib, shards, run_split, coracle):  # noqa: F811
     from pybitmessage_amd import proofofwork, targets, verify, worker
+    base = workloads.baseline()  # with the engine idle, before the first phase
     phases = PHASES * 3
     per = SOAK_S / len(phases)
     rss = []
@@ -68,7 +76,7 @@ def test_soak_every_entry_point_at_once(gpulib, shards, run_split, coracle):  # 
         run_split(split)
         stop = threading.Event()
         todo = queue.Queue()
-        counts = {'service': 0, 'serial': 0, 'batch': 0, 'verify': 0, 'valid': 0}
+        counts = {'service': 0, 'serial': 0, 'batch': 0, 'verify': 0, 'valid': 0, 'crypto': 0}
         stats = {'minimal': 0, 'valid_only': 0}
         bad, crashed = [], []
         lock = threading.Lock()
@@ -131,6 +139,17 @@ def test_soak_every_entry_point_at_once(gpulib, shards, run_split, coracle):  # 
                     counts['verify'] += len(objs)
                     counts['valid'] += sum(got)
 
+        @guard
+        def crypto_loop(at):
+            wl = workloads.workloads()
+            while not stop.is_set():
+                w = wl[at % len(wl)]
+                if w() != base[w.name]:
+                    bad.append(('crypto', w.name))
+                with lock:
+                    counts['crypto'] += 1
+                at += 1
+
         def checker():
             while True:
                 item = todo.get()
@@ -155,7 +174,8 @@ def test_soak_every_entry_point_at_once(gpulib, shards, run_split, coracle):  # 
               threading.Thread(target=serial_loop, args=(rngs[1],)),
               threading.Thread(target=serial_loop, args=(rngs[2],)),
               threading.Thread(target=batch_loop, args=(rngs[3],)),
-              threading.Thread(target=verify_loop, args=(rngs[4],))]
+              threading.Thread(target=verify_loop, args=(rngs[4],)),
+              threading.Thread(target=crypto_loop, args=(5 * p,))]
         t0 = time.time()
         for x in th:
             x.start()

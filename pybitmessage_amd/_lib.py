@@ -367,6 +367,40 @@ RXOPEN_SIGNATURES = [
 ]
 
 
+class BmpowRxObjTables(ctypes.Structure):
+    """``bmpow_rx_obj_tables`` (include/bmpow_rxobjopen.h): the three key tables of one call."""
+    _fields_ = [('n_trial', ctypes.c_size_t), ('trial_priv32', ctypes.c_char_p), ('trial_ripe20', ctypes.c_char_p),
+                ('n_tags', ctypes.c_size_t), ('tag32', ctypes.c_char_p), ('tag_priv32', ctypes.c_char_p),
+                ('n_needed', ctypes.c_size_t), ('needed_tag32', ctypes.c_char_p), ('needed_priv32', ctypes.c_char_p),
+                ('needed_ripe20', ctypes.c_char_p), ('needed_version', ctypes.c_void_p),
+                ('needed_stream', ctypes.c_void_p), ('needed_flags', ctypes.c_char_p)]
+
+
+class BmpowRxSealedObjStats(ctypes.Structure):
+    """``bmpow_rx_sealed_obj_stats`` (include/bmpow_rxobjopen.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64), ('matched', ctypes.c_uint64),
+                ('clear', ctypes.c_uint64), ('sets', ctypes.c_uint64), ('launches', ctypes.c_uint64),
+                ('rx_launches', ctypes.c_uint64), ('tagged_tries', ctypes.c_uint64), ('trial_tries', ctypes.c_uint64),
+                ('bytes_up', ctypes.c_uint64), ('bytes_down', ctypes.c_uint64), ('match_ms', ctypes.c_double),
+                ('open_ms', ctypes.c_double), ('walk_ms', ctypes.c_double), ('hash_ms', ctypes.c_double),
+                ('scalar_ms', ctypes.c_double), ('curve_ms', ctypes.c_double), ('ident_ms', ctypes.c_double),
+                ('finish_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_rxobjopen.h declares
+RXOBJOPEN_SIGNATURES = [
+    ('bmpow_rx_sealed_objects', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p, _p64, ctypes.POINTER(BmpowRxObjTables), ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_rx_sealed_object_plan', ctypes.c_int,
+     [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t),
+      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+      ctypes.POINTER(ctypes.c_int)]),
+    ('bmpow_rx_sealed_obj_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowRxSealedObjStats)]),
+    ('bmpow_rx_sealed_obj_reset_stats', None, []),
+]
+
+
 class BmpowTxRec(ctypes.Structure):
     """``bmpow_tx_rec`` (include/bmpow_tx.h): one built object, 152 bytes."""
     _fields_ = [('status', ctypes.c_int32), ('obj_len', ctypes.c_uint32), ('plain_len', ctypes.c_uint32),
@@ -419,7 +453,7 @@ def load(path=None):
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
                             SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES +
-                            RXOPEN_SIGNATURES):
+                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

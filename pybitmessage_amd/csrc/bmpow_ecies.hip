@@ -15,6 +15,8 @@
 //                    the wave never diverges), x = X / Z^2, one SHA-512 block -> key_e, key_m;
 //   ec_mac_kernel  : per (object, key): HMAC-SHA256 over the object's host-padded blocks, compare, and
 //                    an atomicMin of the key index into match[object].
+// and, for rows that each name their own key (a v5 broadcast's tag, a needed v4 pubkey's address:
+// bmpow_host_rxobjopen.hip), ec_rowkeys_kernel: ec_keys_kernel's work with per-lane digits, one key per row.
 // The two phases stay apart: the ladder costs every lane the same (~2,700 field multiplications), the
 // MAC follows the object's length, and the host sorts the objects by block count so a wave's lanes
 // iterate alike (as the verification pool does).  Every loop bound comes from a host-validated length
@@ -85,6 +87,34 @@ __global__ __launch_bounds__(EC_BLOCK) void ec_raw_kernel(const ge* __restrict__
   if (!finite) ok[o] = 0;
 }
 
+// One key per ROW: lane o runs the ladder over its own table with the digits of key kidx[o] of the table of
+// recoded keys (a v5 broadcast's key is the one filed under its tag, a v4 pubkey's the one of the address that
+// is awaited under its tag), then the SHA-512 block, into kout in ec_keys_kernel's layout for nkeys == 1
+// (plane = stride), so that ec_mac_kernel and ec_gather_kernel take it as they stand.  The digit is a per-lane
+// load (as in ec_raw_kernel); the ladder is branch-free in it, so the wave does not diverge.  A lane whose index
+// is not in the table refuses its row (ok[o] = 0: the MAC kernel skips it) and reads no digit at all.
+__global__ __launch_bounds__(EC_BLOCK) void ec_rowkeys_kernel(const ge* __restrict__ tab, uint32_t n, uint32_t stride,
+                                                              const int32_t* __restrict__ dig, uint32_t ntab,
+                                                              const int32_t* __restrict__ kidx,
+                                                              uint64_t* __restrict__ kout, uint32_t* __restrict__ ok) {
+  const uint32_t o = blockIdx.x * EC_BLOCK + threadIdx.x;
+  if (o >= n) return;
+  const int32_t k = kidx[o];
+  if (k < 0 || (uint32_t)k >= ntab) {
+    ok[o] = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) kout[(size_t)w * stride + o] = 0;
+    return;
+  }
+  fe x;
+  const bool finite = ec::var_mult_x(x, tab, stride, o, dig + (size_t)k * EC_DIGITS);
+  uint64_t h[8];
+  sha512_of_x(h, x);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) kout[(size_t)w * stride + o] = h[w];
+  if (!finite) ok[o] = 0;
+}
+
 __global__ __launch_bounds__(EC_BLOCK) void ec_mac_kernel(const uint64_t* __restrict__ kout, uint32_t n, uint32_t stride,
                                                           uint32_t nkeys, const ec_obj* __restrict__ objs,
                                                           const uint4* __restrict__ pool,
@@ -151,6 +181,16 @@ hipError_t ec_launch_raw(hipStream_t st, const ge* tab, uint32_t n, uint32_t str
   if (n == 0) return hipSuccess;
   if (!ec_shape_ok(n, stride)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ec_raw_kernel, dim3(stride / EC_BLOCK), dim3(EC_BLOCK), 0, st, tab, n, stride, dig, x_out, ok);
+  return hipGetLastError();
+}
+
+hipError_t ec_launch_rowkeys(hipStream_t st, const ge* tab, uint32_t first, uint32_t n, uint32_t stride,
+                             const int32_t* dig, uint32_t ntab, const int32_t* kidx, uint64_t* kout, uint32_t* ok) {
+  if (n == 0) return hipSuccess;
+  if (!ec_shape_ok(n, stride) || first > stride - n || !tab || !dig || !kidx || !kout || !ok) return hipErrorInvalidValue;
+  // rows first .. first + n of the set: every per-row array is entered at `first`, the strides stay the set's
+  hipLaunchKernelGGL(ec_rowkeys_kernel, dim3((n + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, st, tab + first, n, stride,
+                     dig, ntab, kidx, kout + first, ok + first);
   return hipGetLastError();
 }
 

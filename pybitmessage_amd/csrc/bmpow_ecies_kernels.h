@@ -29,6 +29,13 @@ struct ec_obj {
 hipError_t ec_launch_prep(hipStream_t st, const ec::ge* pts, uint32_t n, uint32_t stride, ec::ge* tab, uint32_t* ok);
 hipError_t ec_launch_keys(hipStream_t st, const ec::ge* tab, uint32_t n, uint32_t stride, const int32_t* dig,
                           uint32_t nkeys, uint64_t* kout);
+// One key per row, for rows first .. first + n of the set (first + n <= stride): row first + o takes key kidx[o] of
+// the ntab recoded keys in dig and leaves SHA512(x(key * R)) at kout[w * stride + first + o], the layout of
+// ec_launch_keys for nkeys == 1; ok[first + o] = 0 where kidx[o] is not in 0 .. ntab (no digit is read) or the
+// product is infinite.  ec_launch_mac / ec_launch_gather then run with nkeys == 1, key0 == 0 and kout, objs, ok,
+// match and key_e entered at `first`.
+hipError_t ec_launch_rowkeys(hipStream_t st, const ec::ge* tab, uint32_t first, uint32_t n, uint32_t stride,
+                             const int32_t* dig, uint32_t ntab, const int32_t* kidx, uint64_t* kout, uint32_t* ok);
 // x_out[o] = x(k_o R_o), canonical little-endian limbs; ok[o] &= (k_o R_o is finite)
 hipError_t ec_launch_raw(hipStream_t st, const ec::ge* tab, uint32_t n, uint32_t stride, const int32_t* dig,
                          ec::fe* x_out, uint32_t* ok);

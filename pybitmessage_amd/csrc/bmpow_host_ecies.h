@@ -70,4 +70,15 @@ int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, u
                     const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys, bool want_key_e,
                     bmpow_ecies_stats& st);
 
+// The two halves of ecies_match_set, for a unit whose set holds rows that are not tried against every key
+// (bmpow_host_rxobjopen.hip).  ecies_stage_set: the staging, the uploads, the two memsets and the preparation
+// launch over all n rows, with room in b.kout for the key groups of n_keys keys (at least one key's).
+// ecies_try_keys: the ladder, MAC and gather launches of every key group over rows 0 .. n of a set of n_set
+// rows staged with the same n_keys; nothing is launched for n == 0.  Neither downloads match[].
+int ecies_stage_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, uint32_t n, uint64_t blocks,
+                    const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys, bool want_key_e,
+                    bmpow_ecies_stats& st);
+int ecies_try_keys(Shard& sh, EciesBufs& b, uint32_t n, uint32_t n_set, size_t n_keys, bool want_key_e,
+                   bmpow_ecies_stats& st);
+
 }  // namespace bmhost

@@ -153,6 +153,16 @@ size_t ecies_set_end(const std::vector<Item>& items, size_t i0, uint64_t& blocks
 int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, uint32_t n, uint64_t blocks,
                     const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys, bool want_key_e,
                     bmpow_ecies_stats& st) {
+  if (const int rc = ecies_stage_set(sh, b, h, items, n, blocks, payloads, lens, n_keys, want_key_e, st); rc < 0) return rc;
+  if (const int rc = ecies_try_keys(sh, b, n, n, n_keys, want_key_e, st); rc < 0) return rc;
+  h.match.resize(n);
+  HIPTRY(hipMemcpyAsync(h.match.data(), b.match.get(), n * sizeof(int), hipMemcpyDeviceToHost, sh.stream));
+  return 0;
+}
+
+int ecies_stage_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, uint32_t n, uint64_t blocks,
+                    const uint8_t* const* payloads, const uint64_t* lens, size_t n_keys, bool want_key_e,
+                    bmpow_ecies_stats& st) {
   if (blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "payload pool above 2^32 blocks");
   const uint32_t stride = (n + EC_BLOCK - 1) / EC_BLOCK * EC_BLOCK;
   std::vector<ec::ge>& pts = h.pts;
@@ -201,6 +211,14 @@ int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, u
   HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
   HIPTRY(hipStreamSynchronize(sh.stream));
   if (const int rc = elapsed_into(st.prep_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+  return 0;
+}
+
+int ecies_try_keys(Shard& sh, EciesBufs& b, uint32_t n, uint32_t n_set, size_t n_keys, bool want_key_e,
+                   bmpow_ecies_stats& st) {
+  if (n == 0) return 0;
+  const uint32_t stride = (n_set + EC_BLOCK - 1) / EC_BLOCK * EC_BLOCK;
+  const uint32_t kc = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_keys, kLaunchPairs / stride));  // as staged
   for (size_t k0 = 0; k0 < n_keys; k0 += kc) {
     if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
     const uint32_t nk = (uint32_t)std::min<size_t>(kc, n_keys - k0);
@@ -218,8 +236,6 @@ int ecies_match_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, u
     st.launches++;
     st.pairs += (uint64_t)n * nk;
   }
-  h.match.resize(n);
-  HIPTRY(hipMemcpyAsync(h.match.data(), b.match.get(), n * sizeof(int), hipMemcpyDeviceToHost, sh.stream));
   return 0;
 }
 

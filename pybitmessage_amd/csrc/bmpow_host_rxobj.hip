@@ -1,11 +1,7 @@
 // bmpow_host_rxobj.hip -- the broadcast and pubkey processing's host side: bmpow_rx_objects,
 // bmpow_rx_walk_object and their counters (include/bmpow_rx.h) over the kernels of bmpow_rxobj.hip,
 // bmpow_sig.hip, bmpow_ecies.hip (ec_prep_kernel) and bmpow_ident.hip.
-#include "bmpow_host_rows.h"
-
-#include "../../include/bmpow_rx.h"
-#include "bmpow_rx_fmt.h"
-#include "bmpow_rxobj_kernels.h"
+#include "bmpow_host_rxobj.h"
 
 // One call is run_rows (bmpow_host_rows.h) over the object family; what is an object's own is here: the bound
 // of its signed data, its source (the decrypted payload of a broadcast or an encrypted pubkey, the object
@@ -14,15 +10,6 @@ namespace bmhost {
 namespace {
 
 bmpow_rx_obj_stats g_rxo_stats{};  // under g_mu
-
-struct RxoFamily {
-  using Row = rxo_row;
-  using Pk = rxo_pk;
-  using Rec = bmpow_rx_obj_rec;
-  static constexpr auto walk = rxo_launch_walk;
-  static constexpr auto pack = rxo_launch_pack;
-  static constexpr auto finish = rxo_launch_finish;
-};
 
 struct RxoPolicy {
   const uint8_t* kinds;

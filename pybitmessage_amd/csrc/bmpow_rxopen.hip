@@ -17,15 +17,11 @@
 #include "bmpow_rxopen_kernels.h"
 #include "bmpow_rxopen_rows.h"
 
-__global__ __launch_bounds__(RXS_BLOCK) void rxs_open_kernel(const rxs_row* __restrict__ orows,
-                                                             const uint64_t* __restrict__ key_e, uint32_t n_src,
-                                                             const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain,
-                                                             uint64_t plain_bytes, uint32_t n, int32_t* __restrict__ opened) {
-  __shared__ aes::DecTab tab;
-  aes::fill_dec(tab, threadIdx.x, RXS_BLOCK);
-  __syncthreads();
-  const uint32_t o = blockIdx.x * RXS_BLOCK + threadIdx.x;
-  if (o >= n) return;
+// One lane's row: Row is rx_row (msgs) or rxo_row (broadcasts and pubkeys); both carry poff and plen.
+template <class Row>
+BM_DEV void rxs_open_lane(const aes::DecTab& tab, const rxs_row* __restrict__ orows, const uint64_t* __restrict__ key_e,
+                          uint32_t n_src, const uint8_t* pool, uint64_t pool_bytes, Row* rows, uint8_t* plain,
+                          uint64_t plain_bytes, uint32_t o, int32_t* __restrict__ opened) {
   const rxs_row r = orows[o];
   const uint64_t poff = rows[o].poff, at = 64ull * r.blk;
   // the padded pool row ends behind the ciphertext (bmpow_rxopen_rows.h); the slot holds clen bytes
@@ -50,8 +46,33 @@ __global__ __launch_bounds__(RXS_BLOCK) void rxs_open_kernel(const rxs_row* __re
   opened[o] = got;
 }
 
+__global__ __launch_bounds__(RXS_BLOCK) void rxs_open_kernel(const rxs_row* __restrict__ orows,
+                                                             const uint64_t* __restrict__ key_e, uint32_t n_src,
+                                                             const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain,
+                                                             uint64_t plain_bytes, uint32_t n, int32_t* __restrict__ opened) {
+  __shared__ aes::DecTab tab;
+  aes::fill_dec(tab, threadIdx.x, RXS_BLOCK);
+  __syncthreads();
+  const uint32_t o = blockIdx.x * RXS_BLOCK + threadIdx.x;
+  if (o >= n) return;
+  rxs_open_lane(tab, orows, key_e, n_src, pool, pool_bytes, rows, plain, plain_bytes, o, opened);
+}
+
+// The same over the rows of the object family (bmpow_host_rxobjopen.hip).
+__global__ __launch_bounds__(RXS_BLOCK) void rxo_open_kernel(const rxs_row* __restrict__ orows,
+                                                             const uint64_t* __restrict__ key_e, uint32_t n_src,
+                                                             const uint8_t* pool, uint64_t pool_bytes, rxo_row* rows, uint8_t* plain,
+                                                             uint64_t plain_bytes, uint32_t n, int32_t* __restrict__ opened) {
+  __shared__ aes::DecTab tab;
+  aes::fill_dec(tab, threadIdx.x, RXS_BLOCK);
+  __syncthreads();
+  const uint32_t o = blockIdx.x * RXS_BLOCK + threadIdx.x;
+  if (o >= n) return;
+  rxs_open_lane(tab, orows, key_e, n_src, pool, pool_bytes, rows, plain, plain_bytes, o, opened);
+}
+
 // ---------------------------------------------------------------------------------------
-// Launch wrapper (C++ linkage).
+// Launch wrappers (C++ linkage).
 // ---------------------------------------------------------------------------------------
 hipError_t rxs_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t* key_e, uint32_t n_src,
                            const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain, uint64_t plain_bytes, uint32_t n,
@@ -59,6 +80,16 @@ hipError_t rxs_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t*
   if (n == 0) return hipSuccess;
   if (!orows || !key_e || !pool || !rows || !plain || !opened) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rxs_open_kernel, dim3((n + RXS_BLOCK - 1) / RXS_BLOCK), dim3(RXS_BLOCK), 0, st, orows, key_e, n_src,
+                     pool, pool_bytes, rows, plain, plain_bytes, n, opened);
+  return hipGetLastError();
+}
+
+hipError_t rxo_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t* key_e, uint32_t n_src,
+                           const uint8_t* pool, uint64_t pool_bytes, rxo_row* rows, uint8_t* plain, uint64_t plain_bytes, uint32_t n,
+                           int32_t* opened) {
+  if (n == 0) return hipSuccess;
+  if (!orows || !key_e || !pool || !rows || !plain || !opened) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rxo_open_kernel, dim3((n + RXS_BLOCK - 1) / RXS_BLOCK), dim3(RXS_BLOCK), 0, st, orows, key_e, n_src,
                      pool, pool_bytes, rows, plain, plain_bytes, n, opened);
   return hipGetLastError();
 }

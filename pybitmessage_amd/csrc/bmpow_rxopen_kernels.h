@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bmpow_rx_kernels.h"
+#include "bmpow_rxobj_kernels.h"
 
 constexpr uint32_t RXS_BLOCK = 64;  // one wave: 64 matched rows
 
@@ -24,4 +25,8 @@ static_assert(sizeof(rxs_row) == 16, "rxs_row is 16 bytes");
 // of them is refused (-1), not run.
 hipError_t rxs_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t* key_e, uint32_t n_src,
                            const uint8_t* pool, uint64_t pool_bytes, rx_row* rows, uint8_t* plain, uint64_t plain_bytes, uint32_t n,
+                           int32_t* opened);
+// The same for rows of the object family (rxo_row: a decrypted broadcast or v4 pubkey), for bmpow_host_rxobjopen.hip.
+hipError_t rxo_launch_open(hipStream_t st, const rxs_row* orows, const uint64_t* key_e, uint32_t n_src,
+                           const uint8_t* pool, uint64_t pool_bytes, rxo_row* rows, uint8_t* plain, uint64_t plain_bytes, uint32_t n,
                            int32_t* opened);

@@ -479,8 +479,10 @@ class OpenedObjects(object):
     plaintext (the object itself for a clear pubkey).  Walked fields are filled as far as the reference gets
     before it returns; ``ripe``, ``fromAddress`` and ``sigHash`` belong to rows whose status is ``OBJ_OK``."""
 
-    def __init__(self, recs, objects, plaintexts):
+    def __init__(self, recs, objects, plaintexts, match=None):
         self.recs, self.objects, self.plaintexts = recs, objects, plaintexts
+        # :func:`open_sealed_objects` only: per row the index into the table that opened it (-1: none)
+        self.match = match
         self.status, self.kind, self.digest = recs['status'], recs['kind'], recs['digest']
         self.objectVersion, self.objectStream = recs['object_version'], recs['object_stream']
         self.senderVersion, self.senderStream = recs['sender_version'], recs['sender_stream']
@@ -680,6 +682,152 @@ def open_pubkeys(objects, needed):
                            [expect[i] for i in live])
         recs[live] = res.recs
     return OpenedObjects(recs, objs, [p or b'' for p in plain])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Broadcasts and pubkeys from wire bytes in one call (``bmpow_rx_sealed_objects``, include/bmpow_rxobjopen.h)
+# ---------------------------------------------------------------------------------------------------------
+NEEDED_DECODED, NEEDED_OWN_TAG = 1, 2
+PLAN_CLEAR, PLAN_V4_SHORT = 4, 5
+
+
+class SealedTables(object):
+    """The three key tables of :func:`open_sealed_objects` as the library takes them: ``trial`` -- ``(ripes,
+    privkeys)`` of the v2 / v3 subscriptions; ``tags`` -- ``(tags, privkeys)`` of the v4+ subscriptions;
+    ``needed`` -- ``(tags, privkeys, ripes, versions, streams, flags)`` of ``neededPubkeys``."""
+
+    def __init__(self, trial=((), ()), tags=((), ()), needed=((), (), (), (), (), ())):
+        self.trial_ripes, self.trial_privs = [bytes(r) for r in trial[0]], [ecies._key32(k) for k in trial[1]]
+        self.tags, self.tag_privs = [bytes(t) for t in tags[0]], [ecies._key32(k) for k in tags[1]]
+        self.needed_tags, self.needed_privs = [bytes(t) for t in needed[0]], [ecies._key32(k) for k in needed[1]]
+        self.needed_ripes = [bytes(r).ljust(20, b'\x00') for r in needed[2]]
+        self.needed_versions, self.needed_streams = [int(v) for v in needed[3]], [int(s) for s in needed[4]]
+        self.needed_flags = [int(f) for f in needed[5]]
+        if len(self.trial_ripes) != len(self.trial_privs) or len(self.tags) != len(self.tag_privs) or not (
+                len(self.needed_tags) == len(self.needed_privs) == len(self.needed_ripes) == len(self.needed_versions) ==
+                len(self.needed_streams) == len(self.needed_flags)):
+            raise ValueError('the columns of a table are equally long')
+        if any(len(r) != 20 for r in self.trial_ripes + self.needed_ripes):
+            raise ValueError('a ripe is 20 bytes')
+        if any(len(t) != 32 for t in self.tags + self.needed_tags):
+            raise ValueError('a tag is 32 bytes')
+
+    def struct(self):
+        """``(bmpow_rx_obj_tables, what it points into)``."""
+        ver = np.array(self.needed_versions, dtype=np.uint64)
+        stream = np.array(self.needed_streams, dtype=np.uint64)
+        keep = (ver, stream)
+        t = _lib.BmpowRxObjTables(
+            len(self.trial_privs), b''.join(self.trial_privs), b''.join(self.trial_ripes),
+            len(self.tags), b''.join(self.tags), b''.join(self.tag_privs),
+            len(self.needed_tags), b''.join(self.needed_tags), b''.join(self.needed_privs), b''.join(self.needed_ripes),
+            ver.ctypes.data, stream.ctypes.data, bytes(self.needed_flags))
+        return t, keep
+
+
+def sealed_tables(subscriptions=(), needed=None):
+    """The :class:`SealedTables` of address strings: ``subscriptions`` as for :func:`open_broadcasts`, ``needed`` as
+    for :func:`open_pubkeys`.  The addresses are resolved once, by one :func:`addresses.address_keys` over the
+    distinct ones."""
+    subs = list(subscriptions)
+    asked = [(bytes(tag), entry if isinstance(entry, str) else entry[0]) for tag, entry in (needed or {}).items()]
+    distinct = list(collections.OrderedDict.fromkeys(subs + [a for _, a in asked]))
+    keys = dict(zip(distinct, addresses.address_keys(distinct)))
+    by_ripe, by_tag = collections.OrderedDict(), collections.OrderedDict()
+    for a in subs:
+        status, version, _stream, _ripe, lookup, priv = keys[a]
+        if status == 'success':
+            (by_ripe if version <= 3 else by_tag).setdefault(lookup, priv)
+    cols = ([], [], [], [], [], [])
+    for tag, a in asked:
+        status, version, stream, ripe, lookup, priv = keys[a]
+        good = status == 'success'
+        own = good and lookup == tag
+        for col, v in zip(cols, (tag, priv if own else b'', ripe if good else b'', version if good else 0,
+                                 stream if good else 0, (NEEDED_DECODED if good else 0) | (NEEDED_OWN_TAG if own else 0))):
+            col.append(v)
+    return SealedTables((list(by_ripe), list(by_ripe.values())), (list(by_tag), list(by_tag.values())), cols)
+
+
+def open_sealed_tables(kinds, objects, tables):
+    """The raw call (``bmpow_rx_sealed_objects``) over tables that are built already (:class:`SealedTables`)."""
+    kinds = [int(k) for k in kinds]
+    objs = [o if type(o) is bytes else bytes(o) for o in objects]
+    if len(kinds) != len(objs):
+        raise ValueError('one kind per object')
+    n = len(objs)
+    recs = np.zeros(n, dtype=OBJ_REC)
+    match = np.full(n, -1, dtype=np.int32)
+    offs, lens = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    if n == 0:
+        return OpenedObjects(recs, objs, [], match)
+    if any(not 0 <= k <= 255 for k in kinds):
+        raise ValueError('a kind is KIND_BROADCAST or KIND_PUBKEY')
+    lib = _lib.get()
+    op = (ctypes.c_char_p * n)(*objs)
+    ol = np.fromiter(map(len, objs), dtype=np.uint64, count=n)
+    arena = np.empty(max(int(ol.sum()), 1), dtype=np.uint8)  # untouched pages cost nothing
+    t, keep = tables.struct()
+    _lib.check(lib, lib.bmpow_rx_sealed_objects(n, bytes(kinds), ctypes.cast(op, ctypes.c_void_p),
+                                                ol.ctypes.data_as(signatures._P64), ctypes.byref(t), recs.ctypes.data,
+                                                match.ctypes.data, arena.ctypes.data, arena.size, offs.ctypes.data,
+                                                lens.ctypes.data), 'bmpow_rx_sealed_objects')
+    del keep
+    return OpenedObjects(recs, objs, _ArenaPlaintexts(arena, offs, lens), match)
+
+
+def open_sealed_objects(kinds, objects, subscriptions=(), needed=None):
+    """:func:`open_broadcasts` and :func:`open_pubkeys` for objects as they came off the wire, in one call on the
+    device (``bmpow_rx_sealed_objects``, ``include/bmpow_rxobjopen.h``): per object its kind (``KIND_BROADCAST`` or
+    ``KIND_PUBKEY``; the call routes a v4 pubkey to ``KIND_PUBKEY_V4`` itself), ``subscriptions`` as for
+    :func:`open_broadcasts` and ``needed`` as for :func:`open_pubkeys`.  The head walks, the tag lookups, the trial
+    decryption of v4 broadcasts, the one-key decryption of v5 broadcasts and v4 pubkeys (each row under its own
+    key, in one launch), the AES pass and everything of :func:`open_objects` happen behind the one library call,
+    with no ciphertext uploaded twice and no key or plaintext on the host in between.  Gives an
+    :class:`OpenedObjects` whose records, statuses and plaintexts are those of the two compositions, bit for bit;
+    ``match[i]`` is the index into the table that opened row ``i`` (-1: none): the v2 / v3 subscriptions in their
+    order for a v4 broadcast, the v4+ subscriptions for a v5 broadcast, ``needed``'s entries for a v4 pubkey, each
+    counted without addresses that do not decode or that repeat an earlier lookup key."""
+    return open_sealed_tables(kinds, objects, sealed_tables(subscriptions, needed))
+
+
+def open_sealed_broadcasts(objects, subscriptions):
+    """:func:`open_broadcasts` in one library call (:func:`open_sealed_objects`)."""
+    objs = list(objects)
+    return open_sealed_objects([KIND_BROADCAST] * len(objs), objs, subscriptions)
+
+
+def open_sealed_pubkeys(objects, needed):
+    """:func:`open_pubkeys` in one library call (:func:`open_sealed_objects`)."""
+    objs = list(objects)
+    return open_sealed_objects([KIND_PUBKEY] * len(objs), objs, (), needed)
+
+
+def sealed_object_plan(kind, obj):
+    """What :func:`open_sealed_objects` decides about one object before any table is looked at or key tried, on
+    the host (``bmpow_rx_sealed_object_plan``): ``(openable, reason, routed_kind, payload_off, tag_off, body_off,
+    clen)`` with ``reason`` one of ``PLAN_OK``, ``PLAN_HEAD``, ``PLAN_PAYLOAD``, ``PLAN_CIPHER``, ``PLAN_CLEAR`` (a
+    pubkey that is not version 4) and ``PLAN_V4_SHORT`` (a v4 pubkey below 350 bytes)."""
+    lib = _lib.host()
+    obj = obj if type(obj) is bytes else bytes(obj)
+    po, to, bo, cl = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    reason, routed = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.check(lib, lib.bmpow_rx_sealed_object_plan(int(kind), obj, len(obj), ctypes.byref(routed), ctypes.byref(po),
+                                                         ctypes.byref(to), ctypes.byref(bo), ctypes.byref(cl),
+                                                         ctypes.byref(reason)), 'bmpow_rx_sealed_object_plan')
+    return rc == 1, reason.value, routed.value, po.value, to.value, bo.value, cl.value
+
+
+def sealed_obj_stats():
+    """The counters of ``bmpow_rx_sealed_objects`` (``bmpow_rx_sealed_obj_stats``) as a dict."""
+    lib = _lib.get()
+    st = _lib.BmpowRxSealedObjStats()
+    _lib.check(lib, lib.bmpow_rx_sealed_obj_get_stats(ctypes.byref(st)), 'bmpow_rx_sealed_obj_get_stats')
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def sealed_obj_reset_stats():
+    _lib.get().bmpow_rx_sealed_obj_reset_stats()
 
 
 def obj_stats():

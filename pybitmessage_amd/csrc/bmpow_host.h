@@ -144,6 +144,22 @@ double now_ms();  // steady clock
 using bmown::DevBuf;
 using bmown::Event;
 using bmown::PinBuf;
+using bmown::WipeDevBuf;
+
+// The device time between two completed events, added to acc: the one way a unit's per-phase counters are fed.
+inline int elapsed(double& acc, const Event& a, const Event& b) {
+  float ms = 0;
+  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
+  acc += ms;
+  return 0;
+}
+
+// k consecutive phases: ev[i] .. ev[i + 1] into *acc[i]
+inline int elapsed_phases(double* const* acc, const Event* ev, int k) {
+  for (int i = 0; i < k; ++i)
+    if (const int rc = elapsed(*acc[i], ev[i], ev[i + 1]); rc < 0) return rc;
+  return 0;
+}
 
 // A shard: a device, or a stream of one.  What every subsystem shares; each subsystem keeps its own
 // per-shard state in a vector indexed like g_shards and releases it in its *_release_shards().

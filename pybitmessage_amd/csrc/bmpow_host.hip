@@ -25,6 +25,11 @@
 //   bmpow_host_ecies.hip   ECIES trial decryption of received msgs (include/bmpow_ecies.h)
 //   bmpow_host_intake.hip  object intake: inventory hashes, header walk and checks (include/bmpow_intake.h)
 //   bmpow_host_sig.hip     ECDSA signature verification of received objects (include/bmpow_sig.h)
+//   bmpow_host_send.hip    public keys, signatures and ECIES encryption of outgoing objects (include/bmpow_send.h)
+//   bmpow_host_seal.hip    the seal and CBC kernels' round trip;   bmpow_host_tx.hip  outgoing objects in one call
+// and what groups of them share: bmpow_host_scalar.h (host only: scalars, range checks, padding, DER, draws,
+// cleansed host owners), bmpow_host_sendkit.h (the send side: KeySet, the sign-again loop, the wall-clock
+// guard), bmpow_seal_plan.h (host only: slots, sets), bmpow_host_sig.h / bmpow_host_rows.h (the receive side).
 #include "bmpow_host.h"
 
 namespace bmhost {

@@ -137,13 +137,6 @@ int ecies_events(EciesBufs& b, int dev) {
   return 0;
 }
 
-int elapsed_into(double& acc, const Event& a, const Event& b) {
-  float ms = 0;
-  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
-  acc += ms;
-  return 0;
-}
-
 size_t ecies_set_end(const std::vector<Item>& items, size_t i0, uint64_t& blocks) {
   const SetCut cut = plan_set(items, i0, [](const Item& it) { return it.nblk; }, kSetObjects, kSetPoolBytes);
   blocks = cut.blocks;
@@ -210,7 +203,7 @@ int ecies_stage_set(Shard& sh, EciesBufs& b, EciesStage& h, const Item* items, u
   HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok.get()));
   HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
   HIPTRY(hipStreamSynchronize(sh.stream));
-  if (const int rc = elapsed_into(st.prep_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+  if (const int rc = elapsed(st.prep_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
   return 0;
 }
 
@@ -231,8 +224,8 @@ int ecies_try_keys(Shard& sh, EciesBufs& b, uint32_t n, uint32_t n_set, size_t n
       HIPTRY(ec_launch_gather(sh.stream, b.kout.get(), n, stride, nk, (int)k0, b.match.get(), b.key_e.get()));
     HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
     HIPTRY(hipStreamSynchronize(sh.stream));
-    if (const int rc = elapsed_into(st.ecdh_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-    if (const int rc = elapsed_into(st.mac_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
+    if (const int rc = elapsed(st.ecdh_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+    if (const int rc = elapsed(st.mac_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
     st.launches++;
     st.pairs += (uint64_t)n * nk;
   }

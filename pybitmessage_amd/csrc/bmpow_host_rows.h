@@ -73,9 +73,7 @@ int launch_set(Shard& sh, SigBufs& b, RowBufs<F>& x, const ec::ge* comb, uint32_
 template <class F, class Stats>
 int phase_times(const RowBufs<F>& x, Stats& st) {
   double* const acc[6] = {&st.walk_ms, &st.hash_ms, &st.scalar_ms, &st.curve_ms, &st.ident_ms, &st.finish_ms};
-  for (int k = 0; k < 6; ++k)
-    if (const int rc = sig_elapsed(*acc[k], x.ev[k], x.ev[k + 1]); rc < 0) return rc;
-  return 0;
+  return elapsed_phases(acc, x.ev, 6);
 }
 
 // One call over rows 0 .. n_all (under g_mu).  The rows, sorted by the upper bound of their signed data's

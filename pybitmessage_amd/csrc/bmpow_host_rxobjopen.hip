@@ -158,7 +158,7 @@ int sealed_run_locked(std::vector<Item>& items, const uint8_t* const* payloads, 
     HIPTRY(hipMemcpyAsync(h.match.data(), b.match.get(), n * sizeof(int), hipMemcpyDeviceToHost, sh.stream));
     HIPTRY(hipStreamSynchronize(sh.stream));
     if (ng)
-      if (const int rc = sig_elapsed(st.match_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
+      if (const int rc = elapsed(st.match_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
     st.sets++;
     st.bytes_up += n * (sizeof(ec::ge) + sizeof(ec_obj)) + h.pool.size();
     st.bytes_down += n * sizeof(int);
@@ -227,7 +227,7 @@ int sealed_run_locked(std::vector<Item>& items, const uint8_t* const* payloads, 
       HIPTRY(hipMemcpyAsync(opened.data(), o.opened.get(), nm * sizeof(int32_t), hipMemcpyDeviceToHost, sh.stream));
       HIPTRY(hipMemcpyAsync(plain.data(), x.plain.get(), poff, hipMemcpyDeviceToHost, sh.stream));
       HIPTRY(hipStreamSynchronize(sh.stream));
-      if (const int rc = sig_elapsed(st.open_ms, o.ev[0], o.ev[1]); rc < 0) return rc;
+      if (const int rc = elapsed(st.open_ms, o.ev[0], o.ev[1]); rc < 0) return rc;
       if (const int rc = phase_times(x, st); rc < 0) return rc;
       st.matched += nm;
       st.launches += 10;

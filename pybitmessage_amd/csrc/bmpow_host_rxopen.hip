@@ -146,7 +146,7 @@ int sealed_run_locked(const std::vector<Item>& items, const uint8_t* const* payl
       HIPTRY(hipMemcpyAsync(opened.data(), o.opened.get(), nm * sizeof(int32_t), hipMemcpyDeviceToHost, sh.stream));
       HIPTRY(hipMemcpyAsync(plain.data(), x.plain.get(), poff, hipMemcpyDeviceToHost, sh.stream));
       HIPTRY(hipStreamSynchronize(sh.stream));
-      if (const int rc = sig_elapsed(st.open_ms, o.ev[0], o.ev[1]); rc < 0) return rc;
+      if (const int rc = elapsed(st.open_ms, o.ev[0], o.ev[1]); rc < 0) return rc;
       bmpow_rx_stats rs{};
       if (const int rc = phase_times(x, rs); rc < 0) return rc;
       st.walk_ms += rs.walk_ms, st.hash_ms += rs.hash_ms, st.scalar_ms += rs.scalar_ms;

@@ -2,9 +2,7 @@
 // the counters, and one set's trip through the seal kernel, which bmpow_host_send.hip calls behind its
 // ladder.  Internal.
 #pragma once
-#include "bmpow_host.h"
-
-#include <memory>
+#include "bmpow_host_sendkit.h"
 
 #include "../../include/bmpow_send.h"
 #include "bmpow_seal_kernels.h"
@@ -25,21 +23,22 @@ constexpr size_t kSealSetPoolBytes = 256ull << 20;
 extern bmpow_seal_stats g_seal_stats;  // under g_mu
 int seal_mode();                       // 0: bmpow_ecies_encrypt seals on the host's threads, 1: on the device
 
-// One call's pool and per-row arrays, on the device and on the host.  The pools hold plaintext: sized once
-// for the call's largest set (a growth would free an unwiped buffer) and zeroed before they are released.
+// One call's pool and per-row arrays, on the device and on the host, for the seal kernel and for the CBC
+// kernel (which also takes a key per row).  Sized once for the call's largest set.  The pools hold plaintext
+// and the keys are keys: their owners zero them before they are released.
 struct SealIo {
-  DevBuf<uint8_t> pool;
+  WipeDevBuf<uint8_t> pool;
+  WipeDevBuf<uint4> keys;  // CBC only: two per row
   DevBuf<sl_row> rows;
   DevBuf<uint4> iv;
-  DevBuf<uint32_t> out_len;
+  DevBuf<int32_t> out_len;  // CBC: -1 for a refused padding; the seal's lengths are below 2^31
   Event ev[4];
-  std::unique_ptr<uint8_t[]> host;  // the pool's staging copy: packed, uploaded, downloaded over, scattered
-  size_t host_bytes = 0;
+  WipedBytes host;  // the pool's staging copy: packed, uploaded, downloaded over, scattered
+  Wiped<uint8_t> hkeys;
   std::vector<sl_row> hrows;
   std::vector<uint8_t> hiv;
-  std::vector<uint32_t> hlen;
-  int init(int dev, size_t max_rows, uint64_t max_pool);
-  ~SealIo();
+  std::vector<int32_t> hlen;
+  int init(int dev, size_t max_rows, uint64_t max_pool, bool with_keys = false);
 };
 
 // Rows 0 .. n of a set in device order: set row j is the caller's row row[j], its slot at off[j] of the pool.

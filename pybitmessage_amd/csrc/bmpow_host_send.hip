@@ -1,17 +1,13 @@
-// bmpow_host_send.hip -- the send side's host unit: range checks and random draws, the set loop that takes
-// public keys, signatures and ECIES key agreements through the device, DER encoding, the AES / HMAC pass
+// bmpow_host_send.hip -- the send side's host unit: the set loop that takes public keys, signatures and ECIES
+// key agreements through the device (range checks, draws and DER from bmpow_host_scalar.h), the AES / HMAC pass
 // of the blobs -- libcrypto on the host's threads, or the seal kernel behind the ladder
 // (bmpow_host_seal.hip), by bmpow_send_set_seal -- and the entry points of include/bmpow_send.h.
-#include "bmpow_host.h"
+#include "bmpow_host_seal.h"
 
-#include <openssl/crypto.h>
 #include <openssl/evp.h>
-#include <openssl/rand.h>
 
 #include "../../include/bmpow_send.h"
-#include "bmpow_ecies_kernels.h"
-#include "bmpow_host_seal.h"
-#include "bmpow_send_kernels.h"
+#include "bmpow_set_plan.h"
 
 // ---------------------------------------------------------------------------------------
 // One call: the rows whose inputs are in range go through the device in sets of at most kSendSetRows
@@ -19,127 +15,27 @@
 // count, descending, so a wave's 64 lanes hash alike).  Per set: upload, then the phases one launch
 // each -- hash, comb, then the signature's scalars, or the ephemeral key's digits, the recipient tables
 // (ec_prep_kernel) and the ladder -- with the abort flag read between sets and before the ladder.  One
-// loop serves the three kinds of call.  The buffers are the call's own (DevBuf owners); those that held
-// a private key, a nonce, an ephemeral key or a derived key are zeroed before they are released, on the
-// device and on the host.  Everything runs on the first shard's device and stream.
+// loop serves the three kinds of call.  The buffers are the call's own: a KeySet (bmpow_host_sendkit.h) for
+// the scalars, their points and the key agreement, SendBufs for the signature's; those that held a private
+// key, a nonce, an ephemeral key or a derived key zero themselves before they are released, on the device
+// (WipeDevBuf) and on the host (Wiped).  Everything runs on the first shard's device and stream.
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
 namespace {
 
 constexpr size_t kSendSetRows = 1u << 18;  // as the signature and ECIES sets: 4,096 waves, 128 MB of key tables
 constexpr size_t kSendSetPoolBytes = 256ull << 20;
-constexpr int kSignPasses = 3;
-
-using sn::sc;
-
-// the range checks and the message padding, as bmpow_host_sig.hip has them
-sc sc_from_be(const uint8_t* b) {  // 32 big-endian bytes
-  sc r;
-  for (int i = 0; i < 8; ++i)
-    r.d[7 - i] = (uint32_t)b[4 * i] << 24 | (uint32_t)b[4 * i + 1] << 16 | (uint32_t)b[4 * i + 2] << 8 | b[4 * i + 3];
-  return r;
-}
-
-void sc_to_be(const uint32_t (&d)[8], uint8_t* out) {
-  for (int w = 0; w < 8; ++w)
-    for (int q = 0; q < 4; ++q) out[4 * w + q] = (uint8_t)(d[7 - w] >> (24 - 8 * q));
-}
-
-bool scalar_in_range(const uint8_t* b) {  // 1 <= b < n
-  const sc a = sc_from_be(b);
-  sc t;
-  return !sn::is_zero(a) && !sn::cond_sub_n(t, a);
-}
-
-bool coord_in_range(const sc& a) {  // a < p = 2^256 - 2^32 - 977
-  for (int i = 7; i >= 2; --i)
-    if (a.d[i] != 0xFFFFFFFFu) return true;
-  if (a.d[1] != 0xFFFFFFFEu) return a.d[1] < 0xFFFFFFFEu;
-  return a.d[0] < 0xFFFFFC2Fu;
-}
-
-sg_kw kw_from_be(const uint8_t* b) {
-  sg_kw k;
-  for (int i = 0; i < 4; ++i) k.w[i] = bmsched::load_be64(b + 8 * i);
-  return k;
-}
-
-uint32_t msg_blocks(size_t len) { return (uint32_t)((len + 9 + 63) / 64); }
-
-// data || 0x80 || zeros || the bit length as 8 big-endian bytes, into nblk * 64 bytes
-void pad_blocks(const uint8_t* data, size_t len, uint8_t* dst, uint32_t nblk) {
-  const size_t total = (size_t)nblk * 64;
-  if (len) std::memcpy(dst, data, len);
-  dst[len] = 0x80;
-  std::memset(dst + len + 1, 0, total - len - 1 - 8);
-  const uint64_t bits = (uint64_t)len * 8;
-  for (int j = 0; j < 8; ++j) dst[total - 8 + j] = (uint8_t)(bits >> (56 - 8 * j));
-}
-
-// a host vector that held secrets: sized once (a growth would leave an unwiped copy), zeroed when it dies
-template <class T>
-struct Wiped {
-  std::vector<T> v;
-  ~Wiped() {
-    if (!v.empty()) OPENSSL_cleanse(v.data(), v.size() * sizeof(T));
-  }
-};
-
-bool draw_bytes(uint8_t* out, size_t len) {  // RAND_bytes takes an int
-  for (size_t at = 0; at < len; at += 1u << 20)
-    if (RAND_bytes(out + at, (int)std::min<size_t>(1u << 20, len - at)) != 1) return false;
-  return true;
-}
-
-// 32 random bytes in [1, n - 1], by rejection (the excluded share is 2^-128)
-bool draw_scalar(uint8_t out[32]) {
-  do {
-    if (RAND_bytes(out, 32) != 1) return false;
-  } while (!scalar_in_range(out));
-  return true;
-}
-
-// n of them: one draw for all, then the rejected rows again
-bool draw_scalars(uint8_t* out, size_t n) {
-  if (!draw_bytes(out, 32 * n)) return false;
-  for (size_t i = 0; i < n; ++i)
-    if (!scalar_in_range(out + 32 * i) && !draw_scalar(out + 32 * i)) return false;
-  return true;
-}
 
 bmpow_send_stats g_send_stats{};  // under g_mu
 
-struct SendBufs {  // one call's buffers on the device
-  DevBuf<sg_kw> kw;
-  DevBuf<sc> d, e, rs;
+struct SendBufs {  // one call's buffers on the device, beside its KeySet
+  WipeDevBuf<sc> d;
+  DevBuf<sc> e, rs;
   DevBuf<sg_sig> sigs;
   DevBuf<uint4> pool;
-  DevBuf<ec::ge> pt, pts, tab;
-  DevBuf<int8_t> dig;
-  DevBuf<uint64_t> kout;
-  DevBuf<uint32_t> ok32;
   DevBuf<uint8_t> ok8;
   Event ev[5];
-
-  template <class T>
-  static void wipe(const DevBuf<T>& b) {
-    if (b && !bmown::g_exiting.load(std::memory_order_relaxed) && hipSetDevice(b.dev()) == hipSuccess)
-      (void)hipMemset(b.get(), 0, b.cap() * sizeof(T));
-  }
-  ~SendBufs() {  // before the members' own destructors free them
-    wipe(kw);
-    wipe(d);
-    wipe(dig);
-    wipe(kout);
-  }
 };
-
-int send_elapsed(double& acc, const Event& a, const Event& b) {
-  float ms = 0;
-  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
-  acc += ms;
-  return 0;
-}
 
 enum SendMode { kModePubkeys, kModeSign, kModeEncrypt };
 
@@ -170,74 +66,61 @@ struct SendCall {
 };
 
 int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
-  const bool hashing = c.mode == kModeSign && c.msgs;
+  const bool hashing = c.mode == kModeSign && c.msgs, sign = c.mode == kModeSign, agree = c.mode == kModeEncrypt;
+  // The order and the sets.  Messages to hash go by block count, descending, and are cut as the receive side
+  // cuts its own (plan_set: rows and pool bytes), and so are the rows with nothing to hash (no blocks: rows
+  // alone); plaintexts to seal go by AES block count and are laid out in slots by the seal's planner.
+  const auto blocks_of = [&](uint32_t row) { return hashing ? msg_blocks(c.msg_lens[row]) : 0u; };
+  bmseal::SlotPlan p;
   if (hashing)
-    std::stable_sort(rows.begin(), rows.end(),
-                     [&](uint32_t a, uint32_t b) { return msg_blocks(c.msg_lens[a]) > msg_blocks(c.msg_lens[b]); });
-  // the seal's sets: the rows by AES block count, descending, cut by the planner (rows and pool bytes)
-  std::vector<uint64_t> seal_slot, seal_off;
-  std::vector<uint32_t> seal_set_of;
-  uint64_t seal_max_pool = 16;
+    std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return blocks_of(a) > blocks_of(b); });
   if (c.seal) {
     std::stable_sort(rows.begin(), rows.end(), [&](uint32_t a, uint32_t b) { return c.lens[a] / 16 > c.lens[b] / 16; });
-    seal_slot.resize(rows.size()), seal_off.resize(rows.size()), seal_set_of.resize(rows.size());
-    for (size_t i = 0; i < rows.size(); ++i) seal_slot[i] = bmseal::seal_slot_bytes(c.lens[rows[i]]);
-    if (bmseal::plan_slots(rows.size(), seal_slot.data(), kSendSetRows, kSendSetPoolBytes, seal_set_of.data(),
-                           seal_off.data()) < 0)
-      return set_err(BMPOW_E_ARG, "seal plan refused");
-    for (size_t i = 0; i < rows.size(); ++i) seal_max_pool = std::max(seal_max_pool, seal_off[i] + seal_slot[i]);
+    p.slot.reserve(rows.size());
+    for (uint32_t row : rows) p.slot.push_back(bmseal::seal_slot_bytes(c.lens[row]));
+    if (!p.plan(kSendSetRows, kSendSetPoolBytes)) return set_err(BMPOW_E_ARG, "seal plan refused");
   }
   Shard& sh = g_shards[0];
   HIPTRY(hipSetDevice(sh.dev));
   const ec::ge* comb = nullptr;
   if (const int rc = addr_comb16_table(sh, &comb); rc < 0) return rc;
   SendBufs b;
+  KeySet ks;
   for (Event& e : b.ev) HIPTRY(e.alloc(sh.dev));
   g_send_stats.calls++;
 
-  const size_t cap = std::min(rows.size(), kSendSetRows), cap_stride = (cap + SD_BLOCK - 1) / SD_BLOCK * SD_BLOCK;
-  Wiped<sg_kw> kw;
+  // the buffers that hold secrets, on the device and on the host, sized once for the largest set
+  const size_t cap = std::min(rows.size(), kSendSetRows), cap_stride = round_up((uint32_t)cap, SD_BLOCK);
+  if (const int rc = ks.alloc(sh.dev, cap_stride, agree); rc < 0) return rc;
   Wiped<sc> d;
   Wiped<uint64_t> kout;
-  kw.v.resize(cap);
-  if (c.mode == kModeSign) d.v.resize(cap);
-  if (c.mode == kModeEncrypt && !c.seal) kout.v.resize(8 * cap_stride);
+  if (sign) {
+    d.v.resize(cap);
+    HIPTRY(b.d.alloc(sh.dev, cap_stride));
+  }
+  if (agree && !c.seal) kout.v.resize(8 * cap_stride);
   SealIo sio;
   if (c.seal) {
-    if (const int rc = sio.init(sh.dev, cap, seal_max_pool); rc < 0) return rc;
+    if (const int rc = sio.init(sh.dev, cap, p.sets.max_pool); rc < 0) return rc;
     g_seal_stats.calls++;
-  }
-  // the device buffers that hold secrets, sized once for the largest set: a later growth would free an
-  // unwiped one
-  HIPTRY(b.kw.alloc(sh.dev, cap_stride));
-  if (c.mode == kModeSign) HIPTRY(b.d.alloc(sh.dev, cap_stride));
-  if (c.mode == kModeEncrypt) {
-    HIPTRY(b.dig.alloc(sh.dev, (size_t)SG_DIGITS * cap_stride));
-    HIPTRY(b.kout.alloc(sh.dev, (size_t)8 * cap_stride));
   }
   std::vector<sc> e, rs;
   std::vector<sg_sig> sigs;
   std::vector<uint8_t> pool, ok8;
-  std::vector<ec::ge> pts, pt;
+  std::vector<ec::ge> pt;
   std::vector<uint32_t> ok32;
-  size_t i0 = 0;
-  while (i0 < rows.size()) {
+  for (size_t i0 = 0, k = 0; i0 < rows.size(); ++k) {
     if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
-    size_t i1 = i0;
-    uint64_t blocks = 0;
-    while (i1 < rows.size() && i1 - i0 < kSendSetRows) {
-      const uint32_t nb = hashing ? msg_blocks(c.msg_lens[rows[i1]]) : 0;
-      if (i1 != i0 && (blocks + nb) * 64 > kSendSetPoolBytes) break;
-      if (c.seal && seal_set_of[i1] != seal_set_of[i0]) break;
-      blocks += nb;
-      ++i1;
+    const SetCut cut = c.seal ? SetCut{p.sets.begin[k + 1], 0} : plan_set(rows, i0, blocks_of, kSendSetRows, kSendSetPoolBytes);
+    if (cut.blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "message pool above 2^32 blocks");
+    const size_t i1 = cut.i1;
+    const uint32_t n = (uint32_t)(i1 - i0), stride = round_up(n, SD_BLOCK);
+    for (uint32_t j = 0; j < n; ++j) {
+      const size_t row = rows[i0 + j];
+      ks.stage(j, c.scalars + 32 * row, agree ? c.pubkeys + 64 * row : nullptr);
     }
-    if (blocks > 0xffffffffull) return set_err(BMPOW_E_ARG, "message pool above 2^32 blocks");
-    const uint32_t n = (uint32_t)(i1 - i0), stride = (n + SD_BLOCK - 1) / SD_BLOCK * SD_BLOCK;
-    for (uint32_t j = 0; j < n; ++j) kw.v[j] = kw_from_be(c.scalars + 32 * (size_t)rows[i0 + j]);
-    HIPTRY(b.pt.grow(sh.dev, stride));
-    HIPTRY(hipMemcpyAsync(b.kw.get(), kw.v.data(), n * sizeof(sg_kw), hipMemcpyHostToDevice, sh.stream));
-    if (c.mode == kModeSign) {
+    if (const int rc = ks.upload(sh.stream, n); rc < 0) return rc;
+    if (sign) {
       for (uint32_t j = 0; j < n; ++j) d.v[j] = sc_from_be(c.priv + 32 * (size_t)rows[i0 + j]);
       HIPTRY(b.e.grow(sh.dev, (size_t)2 * stride));
       HIPTRY(b.rs.grow(sh.dev, (size_t)2 * stride));
@@ -245,11 +128,11 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
       HIPTRY(hipMemcpyAsync(b.d.get(), d.v.data(), n * sizeof(sc), hipMemcpyHostToDevice, sh.stream));
       if (hashing) {
         sigs.assign(n, sg_sig{});
-        pool.resize(blocks * 64);
+        pool.resize(cut.blocks * 64);
         uint32_t blk = 0;
         for (uint32_t j = 0; j < n; ++j) {
           sigs[j].blk = blk;
-          sigs[j].nblk = msg_blocks(c.msg_lens[rows[i0 + j]]);
+          sigs[j].nblk = blocks_of(rows[i0 + j]);
           blk += sigs[j].nblk;
         }
         bmsched::parallel_for(n, 1024, [&](size_t a, size_t z) {
@@ -267,20 +150,9 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
         for (uint32_t j = 0; j < n; ++j) e[j] = sc_from_be(c.digests + 32 * (size_t)rows[i0 + j]);
         HIPTRY(hipMemcpyAsync(b.e.get(), e.data(), n * sizeof(sc), hipMemcpyHostToDevice, sh.stream));
       }
-    } else if (c.mode == kModeEncrypt) {
-      pts.resize(n);
-      for (uint32_t j = 0; j < n; ++j) {
-        const uint8_t* q = c.pubkeys + 64 * (size_t)rows[i0 + j];
-        const sc x = sc_from_be(q), y = sc_from_be(q + 32);
-        for (int i = 0; i < 8; ++i) pts[j].x.d[i] = x.d[i], pts[j].y.d[i] = y.d[i];
-      }
-      HIPTRY(b.pts.grow(sh.dev, stride));
-      HIPTRY(b.tab.grow(sh.dev, (size_t)EC_ENTRIES * stride));
-      HIPTRY(b.ok32.grow(sh.dev, stride));
-      HIPTRY(hipMemcpyAsync(b.pts.get(), pts.data(), n * sizeof(ec::ge), hipMemcpyHostToDevice, sh.stream));
     }
     // the selected digest's plane of e: SHA-1 first, SHA-256 behind it; a given digest is the first
-    const sc* e_dev = c.mode == kModeSign ? b.e.get() + (hashing && c.digest == BMPOW_SIG_SHA256 ? stride : 0) : nullptr;
+    const sc* e_dev = sign ? b.e.get() + (hashing && c.digest == BMPOW_SIG_SHA256 ? stride : 0) : nullptr;
     uint64_t launches = 1;
     HIPTRY(hipEventRecord(b.ev[0].get(), sh.stream));
     if (hashing) {
@@ -288,27 +160,28 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
       ++launches;
     }
     HIPTRY(hipEventRecord(b.ev[1].get(), sh.stream));
-    HIPTRY(sd_launch_comb(sh.stream, comb, b.kw.get(), n, stride, b.pt.get()));
-    HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
-    if (c.mode == kModeSign) {
-      HIPTRY(sd_launch_sign(sh.stream, b.pt.get(), b.kw.get(), b.d.get(), e_dev, n, stride, b.rs.get(), b.ok8.get()));
+    if (agree) {
+      if (const int rc = ks.launch_ephemeral(sh.stream, comb, n, stride, &b.ev[2]); rc < 0) return rc;
       ++launches;
-    } else if (c.mode == kModeEncrypt) {
-      HIPTRY(sd_launch_digits(sh.stream, b.kw.get(), n, stride, b.dig.get()));
-      ++launches;
+    } else {
+      HIPTRY(sd_launch_comb(sh.stream, comb, ks.kw.get(), n, stride, ks.pt.get()));
+      HIPTRY(hipEventRecord(b.ev[2].get(), sh.stream));
+      if (sign) {
+        HIPTRY(sd_launch_sign(sh.stream, ks.pt.get(), ks.kw.get(), b.d.get(), e_dev, n, stride, b.rs.get(), b.ok8.get()));
+        ++launches;
+      }
     }
     HIPTRY(hipEventRecord(b.ev[3].get(), sh.stream));
-    if (c.mode == kModeEncrypt) {
+    if (agree) {
       if (g_abort.load()) {
         HIPTRY(hipStreamSynchronize(sh.stream));
         return set_err(BMPOW_E_ABORTED, "aborted");
       }
-      HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), n, stride, b.tab.get(), b.ok32.get()));
-      HIPTRY(sd_launch_shared(sh.stream, b.tab.get(), n, stride, b.dig.get(), b.kout.get()));
+      if (const int rc = ks.launch_shared(sh.stream, n, stride); rc < 0) return rc;
       launches += 2;
     }
     HIPTRY(hipEventRecord(b.ev[4].get(), sh.stream));
-    if (c.mode == kModeSign) {
+    if (sign) {
       rs.resize((size_t)2 * stride);
       ok8.resize(n);
       HIPTRY(hipMemcpyAsync(rs.data(), b.rs.get(), rs.size() * sizeof(sc), hipMemcpyDeviceToHost, sh.stream));
@@ -316,28 +189,28 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
     } else if (c.seal) {
       SealSet s;
       s.n = n, s.stride = stride;
-      s.row = rows.data() + i0, s.off = seal_off.data() + i0;
-      s.pool_bytes = seal_off[i1 - 1] + seal_slot[i1 - 1];
+      s.row = rows.data() + i0, s.off = p.off.data() + i0;
+      s.pool_bytes = p.pool_bytes(k);
       s.plains = c.plains, s.lens = c.lens, s.ivs = c.ivs, s.outs = c.outs, s.out_lens = c.out_lens;
-      if (const int rc = seal_set(sh, sio, s, b.kout.get(), b.pt.get(), b.ok32.get()); rc < 0) return rc;
+      if (const int rc = seal_set(sh, sio, s, ks.kout.get(), ks.pt.get(), ks.ok32.get()); rc < 0) return rc;
     } else {
       pt.resize(n);
-      HIPTRY(hipMemcpyAsync(pt.data(), b.pt.get(), n * sizeof(ec::ge), hipMemcpyDeviceToHost, sh.stream));
-      if (c.mode == kModeEncrypt) {
+      HIPTRY(hipMemcpyAsync(pt.data(), ks.pt.get(), n * sizeof(ec::ge), hipMemcpyDeviceToHost, sh.stream));
+      if (agree) {
         ok32.resize(n);
-        HIPTRY(hipMemcpyAsync(ok32.data(), b.ok32.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, sh.stream));
-        HIPTRY(hipMemcpyAsync(kout.v.data(), b.kout.get(), (size_t)8 * stride * sizeof(uint64_t), hipMemcpyDeviceToHost,
+        HIPTRY(hipMemcpyAsync(ok32.data(), ks.ok32.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, sh.stream));
+        HIPTRY(hipMemcpyAsync(kout.v.data(), ks.kout.get(), (size_t)8 * stride * sizeof(uint64_t), hipMemcpyDeviceToHost,
                               sh.stream));
       }
     }
     HIPTRY(hipStreamSynchronize(sh.stream));
-    if (const int rc = send_elapsed(g_send_stats.hash_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-    if (const int rc = send_elapsed(g_send_stats.comb_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
-    if (const int rc = send_elapsed(g_send_stats.scalar_ms, b.ev[2], b.ev[3]); rc < 0) return rc;
-    if (const int rc = send_elapsed(g_send_stats.ladder_ms, b.ev[3], b.ev[4]); rc < 0) return rc;
+    // with nothing hashed ev[0] .. ev[1] is the gap between two records, no phase: hash_ms stays as it is
+    double* const acc[4] = {&g_send_stats.hash_ms, &g_send_stats.comb_ms, &g_send_stats.scalar_ms, &g_send_stats.ladder_ms};
+    const int skip = hashing ? 0 : 1;
+    if (const int rc = elapsed_phases(acc + skip, b.ev + skip, 4 - skip); rc < 0) return rc;
     for (uint32_t j = 0; j < n && !c.seal; ++j) {
       const size_t row = rows[i0 + j];
-      if (c.mode == kModeSign) {
+      if (sign) {
         c.ok[row] = ok8[j] ? 1 : 0;
         if (ok8[j]) {
           sc_to_be(rs[j].d, c.rs + 64 * row);
@@ -348,7 +221,7 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
       sc_to_be(pt[j].x.d, c.xy + 64 * row);
       sc_to_be(pt[j].y.d, c.xy + 64 * row + 32);
       c.ok[row] = 1;
-      if (c.mode == kModeEncrypt) {
+      if (agree) {
         c.ok[row] = ok32[j] ? 1 : 0;
         if (ok32[j])
           for (int w = 0; w < 8; ++w)
@@ -363,43 +236,11 @@ int send_run_locked(const SendCall& c, std::vector<uint32_t>& rows) {
   return 0;
 }
 
-struct CallClock {  // the call's wall time into host_ms, on every return path (under g_mu)
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  ~CallClock() {
-    g_send_stats.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-};
-
 int run_rows(const SendCall& c, std::vector<uint32_t>& rows) {
   if (rows.empty()) return 0;
   int rc = init_locked();
   if (rc >= 0) rc = send_run_locked(c, rows);
   return rc > 0 ? 0 : rc;
-}
-
-// a DER INTEGER of the 32 big-endian bytes v (not all zero): minimal, a 0x00 in front of a set top bit
-size_t der_int(const uint8_t* v, uint8_t* out) {
-  size_t skip = 0;
-  while (skip < 31 && v[skip] == 0) ++skip;
-  const size_t pad = v[skip] & 0x80 ? 1 : 0, l = 32 - skip + pad;
-  out[0] = 0x02;
-  out[1] = (uint8_t)l;
-  out[2] = 0;
-  std::memcpy(out + 2 + pad, v + skip, 32 - skip);
-  return 2 + l;
-}
-
-bool all_zero(const uint8_t* p, size_t n) {
-  uint8_t o = 0;
-  for (size_t i = 0; i < n; ++i) o |= p[i];
-  return o == 0;
-}
-
-size_t sig_der(const uint8_t rs[64], uint8_t out[72]) {
-  const size_t lr = der_int(rs, out + 2), ls = der_int(rs + 32, out + 2 + lr);
-  out[0] = 0x30;
-  out[1] = (uint8_t)(lr + ls);  // at most 70: short form
-  return 2 + lr + ls;
 }
 
 // libcrypto's contexts for a run of blobs on one thread.  The algorithms are fetched once for the process:
@@ -480,7 +321,7 @@ int bmpow_ec_pubkeys(size_t n, const uint8_t* priv, uint8_t* pub_out, uint8_t* o
   if (n == 0) return 0;
   if (!priv || !pub_out || !ok) return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffull) return set_err(BMPOW_E_ARG, "too many keys");
-  CallClock clock;
+  WallClock clock{g_send_stats.host_ms};
   std::memset(pub_out, 0, 64 * n);
   std::memset(ok, 0, n);
   std::vector<uint32_t> rows;
@@ -501,7 +342,7 @@ int bmpow_ecdsa_sign_digest(size_t n, const uint8_t* priv, const uint8_t* k, con
   if (n == 0) return 0;
   if (!priv || !k || !e || !rs_out || !ok) return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffull) return set_err(BMPOW_E_ARG, "too many rows");
-  CallClock clock;
+  WallClock clock{g_send_stats.host_ms};
   std::memset(rs_out, 0, 64 * n);
   std::memset(ok, 0, n);
   std::vector<uint32_t> rows;
@@ -532,7 +373,7 @@ int bmpow_sig_sign(size_t n, const uint8_t* const* msgs, const uint64_t* msg_len
   if (!msgs || !msg_lens || !privkeys || !sig_out || !sig_len) return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffull) return set_err(BMPOW_E_ARG, "too many messages");
   if (digest != BMPOW_SIG_SHA1 && digest != BMPOW_SIG_SHA256) return set_err(BMPOW_E_ARG, "digest is neither SHA-1 nor SHA-256");
-  CallClock clock;
+  WallClock clock{g_send_stats.host_ms};
   std::memset(sig_out, 0, 72 * n);
   std::memset(sig_len, 0, n);
   for (size_t i = 0; i < n; ++i) {
@@ -558,16 +399,11 @@ int bmpow_sig_sign(size_t n, const uint8_t* const* msgs, const uint64_t* msg_len
   c.ok = ok.data();
   std::vector<uint32_t> rows(n);
   for (size_t i = 0; i < n; ++i) rows[i] = (uint32_t)i;
-  for (int pass = 0; pass < kSignPasses && !rows.empty(); ++pass) {
-    if (const int rc = run_rows(c, rows); rc < 0) return rc;
-    if (nonces) break;
-    std::vector<uint32_t> again;  // r == 0 or s == 0: one row in 2^127; another nonce
-    for (uint32_t row : rows)
-      if (!ok[row]) again.push_back(row);
-    for (uint32_t row : again)
-      if (!draw_scalar(drawn.v.data() + 32 * (size_t)row)) return set_err(BMPOW_E_ARG, "RAND_bytes failed");
-    rows.swap(again);
-  }
+  if (const int rc = sign_passes(
+          rows, nonces ? nullptr : drawn.v.data(), [&](std::vector<uint32_t>& r) { return run_rows(c, r); },
+          [&](uint32_t row) { return !ok[row]; });
+      rc < 0)
+    return rc;
   for (size_t i = 0; i < n; ++i)
     if (ok[i]) sig_len[i] = (uint8_t)sig_der(rs.data() + 64 * i, sig_out + 72 * i);
   return 0;
@@ -587,7 +423,7 @@ int bmpow_ecies_encrypt(size_t n, const uint8_t* const* plains, const uint64_t* 
   if (n == 0) return 0;
   if (!plains || !lens || !pubkeys || !outs || !out_caps || !out_lens) return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffull) return set_err(BMPOW_E_ARG, "too many plaintexts");
-  CallClock clock;
+  WallClock clock{g_send_stats.host_ms};
   std::memset(out_lens, 0, n * sizeof(uint64_t));
   for (size_t i = 0; i < n; ++i) {
     if ((lens[i] && !plains[i]) || !outs[i]) return set_err(BMPOW_E_ARG, "null plaintext or output pointer");
@@ -647,7 +483,7 @@ int bmpow_ecies_encrypt(size_t n, const uint8_t* const* plains, const uint64_t* 
       else out_lens[i] = (uint64_t)l;
     }
   });
-  g_send_stats.seal_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_seal).count();
+  g_send_stats.seal_ms += ms_since(t_seal);
   if (failed.load()) return set_err(BMPOW_E_ARG, "libcrypto refused the AES or HMAC pass");
   return 0;
 }

@@ -36,11 +36,4 @@ struct SigBufs {  // one call's buffers on the device
 // every caller's scalar and curve phases.  The events around the four are the caller's own.
 int sig_launch_verify(Shard& sh, SigBufs& b, const ec::ge* comb, uint32_t n, uint32_t stride, int nhash, const Event& mid);
 
-inline int sig_elapsed(double& acc, const Event& a, const Event& b) {
-  float ms = 0;
-  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
-  acc += ms;
-  return 0;
-}
-
 }  // namespace bmhost

@@ -1,8 +1,10 @@
-// bmpow_host_sig.hip -- the signature verification's host side: strict DER parsing, the padded message
-// pool, and the bmpow_sig_* / bmpow_ecdsa_verify_digest entry points (include/bmpow_sig.h).
+// bmpow_host_sig.hip -- the signature verification's host side: the padded message pool and the
+// bmpow_sig_* / bmpow_ecdsa_verify_digest entry points (include/bmpow_sig.h); the strict DER parser and the
+// range checks are bmpow_host_scalar.h's.
 #include "bmpow_host.h"
 
 #include "../../include/bmpow_sig.h"
+#include "bmpow_host_scalar.h"
 #include "bmpow_host_sig.h"
 
 // ---------------------------------------------------------------------------------------
@@ -45,68 +47,10 @@ namespace {
 
 using sn::sc;
 
-sc sc_from_be(const uint8_t* b) {  // 32 big-endian bytes
-  sc r;
-  for (int i = 0; i < 8; ++i)
-    r.d[7 - i] = (uint32_t)b[4 * i] << 24 | (uint32_t)b[4 * i + 1] << 16 | (uint32_t)b[4 * i + 2] << 8 | b[4 * i + 3];
-  return r;
-}
-
-bool sc_in_range(const sc& a) {  // 1 <= a < n
-  sc t;
-  return !sn::is_zero(a) && !sn::cond_sub_n(t, a);
-}
-
-bool coord_in_range(const sc& a) {  // a < p = 2^256 - 2^32 - 977
-  for (int i = 7; i >= 2; --i)
-    if (a.d[i] != 0xFFFFFFFFu) return true;
-  if (a.d[1] != 0xFFFFFFFEu) return a.d[1] < 0xFFFFFFFEu;
-  return a.d[0] < 0xFFFFFC2Fu;
-}
-
 ec::fe fe_from_sc(const sc& a) {
   ec::fe f;
   for (int i = 0; i < 8; ++i) f.d[i] = a.d[i];
   return f;
-}
-
-// One DER INTEGER at p[pos ..): minimal, non-negative, at most 32 value bytes; out = its 32-byte
-// big-endian value, pos moved past it.
-bool der_int(const uint8_t* p, size_t len, size_t& pos, uint8_t out[32]) {
-  if (len - pos < 2 || p[pos] != 0x02) return false;
-  size_t l = p[pos + 1];
-  if (l == 0 || l >= 0x80 || len - pos - 2 < l) return false;
-  const uint8_t* v = p + pos + 2;
-  if (v[0] & 0x80) return false;                           // negative
-  if (l > 1 && v[0] == 0 && !(v[1] & 0x80)) return false;  // a zero byte the sign does not need
-  pos += 2 + l;
-  if (v[0] == 0) ++v, --l;
-  if (l > 32) return false;
-  std::memset(out, 0, 32 - l);
-  std::memcpy(out + 32 - l, v, l);
-  return true;
-}
-
-bool sig_parse(const uint8_t* p, size_t len, uint8_t rs[64]) {
-  if (len < 8 || p[0] != 0x30 || p[1] >= 0x80 || (size_t)p[1] != len - 2) return false;
-  size_t pos = 2;
-  uint8_t tmp[64];
-  if (!der_int(p, len, pos, tmp) || !der_int(p, len, pos, tmp + 32) || pos != len) return false;
-  if (!sc_in_range(sc_from_be(tmp)) || !sc_in_range(sc_from_be(tmp + 32))) return false;
-  std::memcpy(rs, tmp, 64);
-  return true;
-}
-
-uint32_t msg_blocks(size_t len) { return (uint32_t)((len + 9 + 63) / 64); }
-
-// data || 0x80 || zeros || the bit length as 8 big-endian bytes, into nblk * 64 bytes
-void pad_blocks(const uint8_t* data, size_t len, uint8_t* dst, uint32_t nblk) {
-  const size_t total = (size_t)nblk * 64;
-  if (len) std::memcpy(dst, data, len);
-  dst[len] = 0x80;
-  std::memset(dst + len + 1, 0, total - len - 1 - 8);
-  const uint64_t bits = (uint64_t)len * 8;
-  for (int j = 0; j < 8; ++j) dst[total - 8 + j] = (uint8_t)(bits >> (56 - 8 * j));
 }
 
 bmpow_sig_stats g_sig_stats{};  // under g_mu
@@ -182,9 +126,8 @@ int sig_run_locked(std::vector<SigItem>& items, int nhash, const uint8_t* const*
     out.resize(n);
     HIPTRY(hipMemcpyAsync(out.data(), b.verdict.get(), n, hipMemcpyDeviceToHost, sh.stream));
     HIPTRY(hipStreamSynchronize(sh.stream));
-    if (const int rc = sig_elapsed(g_sig_stats.hash_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-    if (const int rc = sig_elapsed(g_sig_stats.scalar_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
-    if (const int rc = sig_elapsed(g_sig_stats.curve_ms, b.ev[2], b.ev[3]); rc < 0) return rc;
+    double* const acc[3] = {&g_sig_stats.hash_ms, &g_sig_stats.scalar_ms, &g_sig_stats.curve_ms};
+    if (const int rc = elapsed_phases(acc, b.ev, 3); rc < 0) return rc;
     for (uint32_t j = 0; j < n; ++j) verdict[items[i0 + j].orig] = out[j] <= (uint8_t)nhash ? out[j] : 0;
     g_sig_stats.uploaded += n;
     g_sig_stats.ladders += n;
@@ -228,7 +171,7 @@ int bmpow_ecdsa_verify_digest(size_t n, const uint8_t* pub, const uint8_t* rs, c
     it.nblk = 0;
     it.r = sc_from_be(rs + 64 * i);
     it.s = sc_from_be(rs + 64 * i + 32);
-    if (!sc_in_range(it.r) || !sc_in_range(it.s) || !take_key(pub + 64 * i, it)) continue;
+    if (!scalar_in_range(it.r) || !scalar_in_range(it.s) || !take_key(pub + 64 * i, it)) continue;
     items.push_back(it);
   }
   int rc = 0;

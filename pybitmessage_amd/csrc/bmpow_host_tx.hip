@@ -2,15 +2,11 @@
 // checks, random draws, the set loop that takes head and body bytes through packing, hashing, signing, the
 // tail, the ECIES key agreement, the seal and the payload's SHA-512 on the device, the scatter of the
 // payloads, and the entry points of include/bmpow_tx.h.
-#include "bmpow_host.h"
-
-#include <openssl/crypto.h>
-#include <openssl/rand.h>
+#include "bmpow_host_sendkit.h"
 
 #include "../../include/bmpow_tx.h"
-#include "bmpow_ecies_kernels.h"
+#include "bmpow_seal_kernels.h"
 #include "bmpow_seal_plan.h"
-#include "bmpow_send_kernels.h"
 #include "bmpow_tx_fmt.h"
 #include "bmpow_tx_kernels.h"
 
@@ -23,124 +19,41 @@
 // once, with the row structs, keys, nonces, ephemeral keys, IVs and recipient points; then the launches, one
 // per phase, the sealed rows' (the set's first ns) between the tail and the finish; the pool and the
 // records come down.  The abort flag is read between sets and before the ladder.  The buffers are the
-// call's own (DevBuf owners), sized once for its largest set; those that held a private key, a nonce, an
-// ephemeral key, a derived key or plaintext are zeroed before they are released, on the device and on the
-// host.  Everything runs on the first shard's device and stream.
+// call's own, sized once for its largest set: TxBufs, and a KeySet (bmpow_host_sendkit.h) for the sealed rows'
+// key agreement; those that held a private key, a nonce, an ephemeral key, a derived key or plaintext zero
+// themselves before they are released, on the device (WipeDevBuf) and on the host (Wiped, WipedBytes).
+// Everything runs on the first shard's device and stream.
 // ---------------------------------------------------------------------------------------
 namespace bmhost {
 namespace {
 
 constexpr size_t kTxSetRows = 1u << 18;
 constexpr size_t kTxSetPoolBytes = 256ull << 20;
-constexpr int kTxPasses = 3;
-
-using sn::sc;
-
-// the range checks and the draws, as bmpow_host_send.hip has them
-sc sc_from_be(const uint8_t* b) {  // 32 big-endian bytes
-  sc r;
-  for (int i = 0; i < 8; ++i)
-    r.d[7 - i] = (uint32_t)b[4 * i] << 24 | (uint32_t)b[4 * i + 1] << 16 | (uint32_t)b[4 * i + 2] << 8 | b[4 * i + 3];
-  return r;
-}
-
-bool scalar_in_range(const uint8_t* b) {  // 1 <= b < n
-  const sc a = sc_from_be(b);
-  sc t;
-  return !sn::is_zero(a) && !sn::cond_sub_n(t, a);
-}
-
-bool coord_in_range(const sc& a) {  // a < p = 2^256 - 2^32 - 977
-  for (int i = 7; i >= 2; --i)
-    if (a.d[i] != 0xFFFFFFFFu) return true;
-  if (a.d[1] != 0xFFFFFFFEu) return a.d[1] < 0xFFFFFFFEu;
-  return a.d[0] < 0xFFFFFC2Fu;
-}
-
-sg_kw kw_from_be(const uint8_t* b) {
-  sg_kw k;
-  for (int i = 0; i < 4; ++i) k.w[i] = bmsched::load_be64(b + 8 * i);
-  return k;
-}
-
-template <class T>
-struct Wiped {  // a host vector that held secrets: sized once, zeroed when it dies
-  std::vector<T> v;
-  ~Wiped() {
-    if (!v.empty()) OPENSSL_cleanse(v.data(), v.size() * sizeof(T));
-  }
-};
-
-bool draw_bytes(uint8_t* out, size_t len) {  // RAND_bytes takes an int
-  for (size_t at = 0; at < len; at += 1u << 20)
-    if (RAND_bytes(out + at, (int)std::min<size_t>(1u << 20, len - at)) != 1) return false;
-  return true;
-}
-
-bool draw_scalar(uint8_t out[32]) {  // [1, n - 1] by rejection
-  do {
-    if (RAND_bytes(out, 32) != 1) return false;
-  } while (!scalar_in_range(out));
-  return true;
-}
-
-bool draw_scalars(uint8_t* out, size_t n) {
-  if (!draw_bytes(out, 32 * n)) return false;
-  for (size_t i = 0; i < n; ++i)
-    if (!scalar_in_range(out + 32 * i) && !draw_scalar(out + 32 * i)) return false;
-  return true;
-}
-
-uint32_t round_up(uint32_t n, uint32_t q) { return (n + q - 1) / q * q; }
 
 bmpow_tx_stats g_tx_stats{};  // under g_mu
 
-struct TxBufs {  // one call's buffers on the device and their staging copies
+struct TxBufs {  // one call's buffers on the device and their staging copies, beside the sealed rows' KeySet
   DevBuf<tx_row> rows;
   DevBuf<sl_row> sl;
-  DevBuf<uint8_t> pool, ok8;
-  DevBuf<uint4> hpool, iv;
+  WipeDevBuf<uint8_t> pool;
+  WipeDevBuf<uint4> hpool;
+  DevBuf<uint8_t> ok8;
+  DevBuf<uint4> iv;
   DevBuf<sg_sig> sigs;
-  DevBuf<sg_kw> kw, kw2;
-  DevBuf<sc> d, e, rs;
-  DevBuf<ec::ge> pt, pt2, pts, tab;
-  DevBuf<int8_t> dig;
-  DevBuf<uint64_t> kout;
-  DevBuf<uint32_t> ok32, blob_len;
+  WipeDevBuf<sg_kw> kw;
+  WipeDevBuf<sc> d;
+  DevBuf<sc> e, rs;
+  DevBuf<ec::ge> pt;
+  DevBuf<uint32_t> blob_len;
   DevBuf<bmpow_tx_rec> recs;
   Event ev[7];
-  std::unique_ptr<uint8_t[]> host;  // the pool's staging copy: packed, uploaded, downloaded over, scattered
-  size_t host_bytes = 0;
-  Wiped<sg_kw> hkw, hkw2;
+  WipedBytes host;  // the pool's staging copy: packed, uploaded, downloaded over, scattered
+  Wiped<sg_kw> hkw;
   Wiped<sc> hd;
   std::vector<tx_row> hrows;
-  std::vector<ec::ge> hpts;
   std::vector<uint8_t> hiv;
   std::vector<bmpow_tx_rec> hrecs;
-
-  template <class T>
-  static void wipe(const DevBuf<T>& b) {
-    if (b && !bmown::g_exiting.load(std::memory_order_relaxed) && hipSetDevice(b.dev()) == hipSuccess)
-      (void)hipMemset(b.get(), 0, b.cap() * sizeof(T));
-  }
-  ~TxBufs() {  // before the members' own destructors free them
-    wipe(kw);
-    wipe(kw2);
-    wipe(d);
-    wipe(dig);
-    wipe(kout);
-    wipe(pool);
-    wipe(hpool);
-    if (host) OPENSSL_cleanse(host.get(), host_bytes);
-  }
 };
-
-int tx_elapsed(double& acc, const Event& a, const Event& b) {
-  float ms = 0;
-  HIPTRY(hipEventElapsedTime(&ms, a.get(), b.get()));
-  acc += ms;
-  return 0;
-}
 
 // The caller's arrays, indexed by the caller's row.
 struct TxCall {
@@ -168,27 +81,27 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
     return c.body_lens[a] > c.body_lens[b];
   });
   const size_t total = rows.size();
-  std::vector<uint64_t> slot(total), off(total);
-  std::vector<uint32_t> set_of(total);
-  for (size_t i = 0; i < total; ++i) slot[i] = txf::slot_bytes(c.body_lens[rows[i]]);
-  if (bmseal::plan_slots(total, slot.data(), kTxSetRows, kTxSetPoolBytes, set_of.data(), off.data()) < 0)
-    return set_err(BMPOW_E_ARG, "slot plan refused");
-  // the largest set: rows, sealed rows, slot pool, hash blocks
-  size_t max_rows = 0, max_sealed = 0;
-  uint64_t max_pool = 16, max_blocks = 1;
-  for (size_t i0 = 0; i0 < total;) {
-    size_t i1 = i0, sealed = 0;
+  bmseal::SlotPlan p;
+  p.slot.resize(total);
+  for (size_t i = 0; i < total; ++i) p.slot[i] = txf::slot_bytes(c.body_lens[rows[i]]);
+  if (!p.plan(kTxSetRows, kTxSetPoolBytes)) return set_err(BMPOW_E_ARG, "slot plan refused");
+  const std::vector<uint64_t>& off = p.off;
+  const std::vector<size_t>& begin = p.sets.begin;
+  // the largest set's sealed rows and hash blocks, beside the planner's rows and slot pool
+  const size_t max_rows = p.sets.max_rows;
+  const uint64_t max_pool = p.sets.max_pool;
+  size_t max_sealed = 0;
+  uint64_t max_blocks = 1;
+  for (size_t k = 0; k < p.sets.count(); ++k) {
+    size_t sealed = 0;
     uint64_t blocks = 0;
-    for (; i1 < total && set_of[i1] == set_of[i0]; ++i1) {
-      const uint32_t row = rows[i1];
+    for (size_t i = begin[k]; i < begin[k + 1]; ++i) {
+      const uint32_t row = rows[i];
       sealed += c.kinds[row] == BMPOW_TX_SEALED;
       blocks += txf::signed_blocks((uint32_t)(c.head_lens[row] + c.body_lens[row]));
     }
-    max_rows = std::max(max_rows, i1 - i0);
     max_sealed = std::max(max_sealed, sealed);
-    max_pool = std::max(max_pool, off[i1 - 1] + slot[i1 - 1]);
     max_blocks = std::max(max_blocks, blocks);
-    i0 = i1;
   }
   if (max_blocks > 0xffffffffull / 4) return set_err(BMPOW_E_ARG, "signed data above 2^30 blocks");
 
@@ -197,9 +110,10 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
   const ec::ge* comb = nullptr;
   if (const int rc = addr_comb16_table(sh, &comb); rc < 0) return rc;
   TxBufs b;
+  KeySet ks;  // the sealed rows (a set's first ns): ephemeral keys and recipient points
   for (Event& e : b.ev) HIPTRY(e.alloc(sh.dev));
   const uint32_t cap = round_up((uint32_t)max_rows, TX_BLOCK), cap_s = round_up((uint32_t)max_sealed, TX_BLOCK);
-  // every buffer sized once for the largest set: a later growth would free an unwiped one
+  // every buffer sized once for the largest set
   HIPTRY(b.rows.alloc(sh.dev, cap));
   HIPTRY(b.sl.alloc(sh.dev, cap));
   HIPTRY(b.pool.alloc(sh.dev, max_pool));
@@ -212,35 +126,25 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
   HIPTRY(b.ok8.alloc(sh.dev, cap));
   HIPTRY(b.pt.alloc(sh.dev, cap));
   HIPTRY(b.recs.alloc(sh.dev, cap));
+  if (const int rc = ks.alloc(sh.dev, cap_s); rc < 0) return rc;
   if (cap_s) {
-    HIPTRY(b.kw2.alloc(sh.dev, cap_s));
-    HIPTRY(b.pt2.alloc(sh.dev, cap_s));
-    HIPTRY(b.pts.alloc(sh.dev, cap_s));
-    HIPTRY(b.tab.alloc(sh.dev, (size_t)EC_ENTRIES * cap_s));
-    HIPTRY(b.dig.alloc(sh.dev, (size_t)SG_DIGITS * cap_s));
-    HIPTRY(b.kout.alloc(sh.dev, (size_t)8 * cap_s));
-    HIPTRY(b.ok32.alloc(sh.dev, cap_s));
     HIPTRY(b.blob_len.alloc(sh.dev, cap_s));
     HIPTRY(b.iv.alloc(sh.dev, cap_s));
   }
-  b.host.reset(new uint8_t[max_pool]);
-  b.host_bytes = max_pool;
+  b.host.alloc(max_pool);
   b.hkw.v.resize(max_rows);
   b.hd.v.resize(max_rows);
-  b.hkw2.v.resize(max_sealed);
   b.hrows.resize(max_rows);
-  b.hpts.resize(max_sealed);
   b.hiv.resize(16 * max_sealed);
   b.hrecs.resize(max_rows);
   uint8_t* hp = b.host.get();
   g_tx_stats.calls++;
 
-  for (size_t i0 = 0; i0 < total;) {
+  for (size_t k = 0; k < p.sets.count(); ++k) {
     if (g_abort.load()) return set_err(BMPOW_E_ABORTED, "aborted");
-    size_t i1 = i0;
-    while (i1 < total && set_of[i1] == set_of[i0]) ++i1;
-    const uint32_t n = (uint32_t)(i1 - i0), stride = round_up(n, TX_BLOCK);
-    const uint64_t pool_bytes = off[i1 - 1] + slot[i1 - 1];
+    const size_t i0 = begin[k];
+    const uint32_t n = (uint32_t)(begin[k + 1] - i0), stride = round_up(n, TX_BLOCK);
+    const uint64_t pool_bytes = p.pool_bytes(k);
     uint32_t ns = 0, blk = 0;
     for (uint32_t j = 0; j < n; ++j) {
       const uint32_t row = rows[i0 + j];
@@ -264,10 +168,7 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
         b.hkw.v[j] = kw_from_be(c.nonces + 32 * row);
         b.hd.v[j] = sc_from_be(c.priv + 32 * row);
         if (j < ns) {
-          b.hkw2.v[j] = kw_from_be(c.ephem + 32 * row);
-          const uint8_t* q = c.pubkeys + 64 * row;
-          const sc x = sc_from_be(q), y = sc_from_be(q + 32);
-          for (int i = 0; i < 8; ++i) b.hpts[j].x.d[i] = x.d[i], b.hpts[j].y.d[i] = y.d[i];
+          ks.stage(j, c.ephem + 32 * row, c.pubkeys + 64 * row);
           std::memcpy(b.hiv.data() + 16 * j, c.ivs + 16 * row, 16);
         }
       }
@@ -277,8 +178,7 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
     HIPTRY(hipMemcpyAsync(b.kw.get(), b.hkw.v.data(), n * sizeof(sg_kw), hipMemcpyHostToDevice, sh.stream));
     HIPTRY(hipMemcpyAsync(b.d.get(), b.hd.v.data(), n * sizeof(sc), hipMemcpyHostToDevice, sh.stream));
     if (ns) {
-      HIPTRY(hipMemcpyAsync(b.kw2.get(), b.hkw2.v.data(), ns * sizeof(sg_kw), hipMemcpyHostToDevice, sh.stream));
-      HIPTRY(hipMemcpyAsync(b.pts.get(), b.hpts.data(), ns * sizeof(ec::ge), hipMemcpyHostToDevice, sh.stream));
+      if (const int rc = ks.upload(sh.stream, ns); rc < 0) return rc;
       HIPTRY(hipMemcpyAsync(b.iv.get(), b.hiv.data(), (size_t)16 * ns, hipMemcpyHostToDevice, sh.stream));
     }
     // the selected digest's plane of e: SHA-1 first, SHA-256 behind it
@@ -299,15 +199,13 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
         HIPTRY(hipStreamSynchronize(sh.stream));
         return set_err(BMPOW_E_ABORTED, "aborted");
       }
-      HIPTRY(sd_launch_comb(sh.stream, comb, b.kw2.get(), ns, stride_s, b.pt2.get()));
-      HIPTRY(sd_launch_digits(sh.stream, b.kw2.get(), ns, stride_s, b.dig.get()));
-      HIPTRY(ec_launch_prep(sh.stream, b.pts.get(), ns, stride_s, b.tab.get(), b.ok32.get()));
-      HIPTRY(sd_launch_shared(sh.stream, b.tab.get(), ns, stride_s, b.dig.get(), b.kout.get()));
+      if (const int rc = ks.launch_ephemeral(sh.stream, comb, ns, stride_s); rc < 0) return rc;
+      if (const int rc = ks.launch_shared(sh.stream, ns, stride_s); rc < 0) return rc;
       launches += 5;
     }
     HIPTRY(hipEventRecord(b.ev[4].get(), sh.stream));
     if (ns)
-      HIPTRY(sl_launch_seal(sh.stream, b.kout.get(), b.pt2.get(), b.ok32.get(), b.iv.get(), b.sl.get(), b.pool.get(), ns,
+      HIPTRY(sl_launch_seal(sh.stream, ks.kout.get(), ks.pt.get(), ks.ok32.get(), b.iv.get(), b.sl.get(), b.pool.get(), ns,
                             stride_s, b.blob_len.get()));
     HIPTRY(hipEventRecord(b.ev[5].get(), sh.stream));
     HIPTRY(tx_launch_finish(sh.stream, b.rows.get(), b.blob_len.get(), ns, b.pool.get(), pool_bytes, n, b.recs.get()));
@@ -315,12 +213,9 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
     HIPTRY(hipMemcpyAsync(hp, b.pool.get(), pool_bytes, hipMemcpyDeviceToHost, sh.stream));
     HIPTRY(hipMemcpyAsync(b.hrecs.data(), b.recs.get(), n * sizeof(bmpow_tx_rec), hipMemcpyDeviceToHost, sh.stream));
     HIPTRY(hipStreamSynchronize(sh.stream));
-    if (const int rc = tx_elapsed(g_tx_stats.pack_ms, b.ev[0], b.ev[1]); rc < 0) return rc;
-    if (const int rc = tx_elapsed(g_tx_stats.hash_ms, b.ev[1], b.ev[2]); rc < 0) return rc;
-    if (const int rc = tx_elapsed(g_tx_stats.sign_ms, b.ev[2], b.ev[3]); rc < 0) return rc;
-    if (const int rc = tx_elapsed(g_tx_stats.ladder_ms, b.ev[3], b.ev[4]); rc < 0) return rc;
-    if (const int rc = tx_elapsed(g_tx_stats.seal_ms, b.ev[4], b.ev[5]); rc < 0) return rc;
-    if (const int rc = tx_elapsed(g_tx_stats.finish_ms, b.ev[5], b.ev[6]); rc < 0) return rc;
+    double* const acc[6] = {&g_tx_stats.pack_ms, &g_tx_stats.hash_ms, &g_tx_stats.sign_ms,
+                            &g_tx_stats.ladder_ms, &g_tx_stats.seal_ms, &g_tx_stats.finish_ms};
+    if (const int rc = elapsed_phases(acc, b.ev, 6); rc < 0) return rc;
     std::atomic<bool> bad{false};
     bmsched::parallel_for(n, 1024, [&](size_t a, size_t z) {
       for (size_t j = a; j < z; ++j) {
@@ -342,17 +237,9 @@ int tx_run_locked(const TxCall& c, std::vector<uint32_t>& rows) {
     g_tx_stats.rows += n;
     g_tx_stats.sets++;
     g_tx_stats.launches += launches;
-    i0 = i1;
   }
   return 0;
 }
-
-struct TxClock {  // the call's wall time into host_ms, on every return path (under g_mu)
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  ~TxClock() {
-    g_tx_stats.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-};
 
 int tx_run(const TxCall& c, std::vector<uint32_t>& rows) {
   if (rows.empty()) return 0;
@@ -378,7 +265,7 @@ int bmpow_tx_objects(size_t n, const uint8_t* kinds, const uint8_t* const* heads
     return set_err(BMPOW_E_ARG, "null pointer");
   if (n > 0xffffffffull) return set_err(BMPOW_E_ARG, "too many objects");
   if (digest != BMPOW_SIG_SHA1 && digest != BMPOW_SIG_SHA256) return set_err(BMPOW_E_ARG, "digest is neither SHA-1 nor SHA-256");
-  TxClock clock;
+  WallClock clock{g_tx_stats.host_ms};
   size_t sealed = 0;
   for (size_t i = 0; i < n; ++i) {
     if (kinds[i] != BMPOW_TX_SEALED && kinds[i] != BMPOW_TX_CLEAR) return set_err(BMPOW_E_ARG, "unknown kind");
@@ -432,17 +319,10 @@ int bmpow_tx_objects(size_t n, const uint8_t* kinds, const uint8_t* const* heads
       r.status = BMPOW_TX_BAD_RECIPIENT;
     else rows.push_back((uint32_t)i);
   }
-  for (int pass = 0; pass < kTxPasses && !rows.empty(); ++pass) {
-    if (const int rc = tx_run(c, rows); rc < 0) return rc;
-    if (nonces) break;
-    std::vector<uint32_t> again;  // r == 0 or s == 0: one row in 2^127; another nonce, the whole chain again
-    for (uint32_t row : rows)
-      if (out[row].status == BMPOW_TX_NO_SIGNATURE) again.push_back(row);
-    for (uint32_t row : again)
-      if (!draw_scalar(k_drawn.v.data() + 32 * (size_t)row)) return set_err(BMPOW_E_ARG, "RAND_bytes failed");
-    rows.swap(again);
-  }
-  return 0;
+  // r == 0 or s == 0: another nonce, the whole chain again
+  return sign_passes(
+      rows, nonces ? nullptr : k_drawn.v.data(), [&](std::vector<uint32_t>& r) { return tx_run(c, r); },
+      [&](uint32_t row) { return out[row].status == BMPOW_TX_NO_SIGNATURE; });
 }
 
 int bmpow_tx_layout_row(uint32_t head_len, uint64_t body_len, bmpow_tx_layout* out) {

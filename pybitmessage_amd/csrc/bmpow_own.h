@@ -4,6 +4,11 @@
 // shard set looks like by then.  The runtime's calls sit behind a traits parameter (an allocate and a free
 // function), defaulted to the HIP one, so tests/native/own_sim.cpp instantiates the same template over a
 // counting stand-in on the CPU.
+//
+// A wiping owner (WipeBuf; Owned<Api, true>) holds secrets: a private key, a nonce, a derived key, plaintext.
+// It zeroes its whole capacity on its own device (the traits' zero function) right before every release --
+// destruction, reset, a second alloc, a grow that reallocates, move-assignment over a live buffer -- so no
+// list of buffers to wipe is kept by hand anywhere.
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -17,7 +22,7 @@ namespace bmown {
 // exit handlers may already have run when a static owner's destructor does.
 inline std::atomic<bool> g_exiting{false};
 
-template <class Api>
+template <class Api, bool Wipe = false>
 class Owned {
  public:
   using err_t = typename Api::err_t;
@@ -37,9 +42,12 @@ class Owned {
   // replaces).  hipFree / hipHostFree wait for the whole device: never call this, or let an owner die,
   // under the engine's mutex -- move it into the shard's retired list instead (engine_launch).
   void reset() {
-    if (p_ && !g_exiting.load(std::memory_order_relaxed)) Api::free(dev_, p_);
+    if (p_ && !g_exiting.load(std::memory_order_relaxed)) {
+      if constexpr (Wipe) Api::zero(dev_, p_, bytes_);
+      Api::free(dev_, p_);
+    }
     p_ = d_ = nullptr;
-    n_ = 0;
+    n_ = bytes_ = 0;
     dev_ = -1;
   }
   size_t cap() const { return n_; }  // elements
@@ -55,6 +63,7 @@ class Owned {
       return e;
     }
     n_ = n;
+    bytes_ = bytes;
     dev_ = dev;
     return e;
   }
@@ -62,16 +71,17 @@ class Owned {
     p_ = std::exchange(o.p_, nullptr);
     d_ = std::exchange(o.d_, nullptr);
     n_ = std::exchange(o.n_, 0);
+    bytes_ = std::exchange(o.bytes_, 0);
     dev_ = std::exchange(o.dev_, -1);
   }
   void* p_ = nullptr;  // what is freed
   void* d_ = nullptr;  // the device's address of it (a mapped pinned buffer; else p_)
-  size_t n_ = 0;
+  size_t n_ = 0, bytes_ = 0;
   int dev_ = -1;
 };
 
-template <class T, class Api>
-class Buf : public Owned<Api> {
+template <class T, class Api, bool Wipe = false>
+class Buf : public Owned<Api, Wipe> {
  public:
   using err_t = typename Api::err_t;
   err_t alloc(int dev, size_t n, unsigned flags = 0) { return this->alloc_bytes(dev, n, n * sizeof(T), flags); }
@@ -82,6 +92,9 @@ class Buf : public Owned<Api> {
   T* dptr() const { return static_cast<T*>(this->d_); }  // as the device addresses it
   T& operator[](size_t i) const { return get()[i]; }
 };
+
+template <class T, class Api>
+using WipeBuf = Buf<T, Api, true>;
 
 }  // namespace bmown
 
@@ -100,6 +113,9 @@ struct HipDev {  // hipMalloc
     return e;
   }
   static void free(int dev, void* p) { (void)hipSetDevice(dev), (void)hipFree(p); }
+  static void zero(int dev, void* p, size_t bytes) {
+    if (hipSetDevice(dev) == hipSuccess) (void)hipMemset(p, 0, bytes);
+  }
 };
 
 struct HipPin {  // hipHostMalloc(flags); a mapped allocation also yields the device's address
@@ -127,6 +143,7 @@ struct HipEvent {  // hipEventCreateWithFlags(flags)
 };
 
 template <class T> using DevBuf = Buf<T, HipDev>;
+template <class T> using WipeDevBuf = WipeBuf<T, HipDev>;  // zeroed on the device before it is released
 template <class T> using PinBuf = Buf<T, HipPin>;
 class Event : public Owned<HipEvent> {
  public:

@@ -1,7 +1,7 @@
 // bmpow_seal_plan.cpp -- see bmpow_seal_plan.h.
 #include "bmpow_seal_plan.h"
 
-#include <vector>
+#include <algorithm>
 
 namespace bmseal {
 
@@ -36,6 +36,18 @@ int64_t plan_seal(size_t n, const uint64_t* lens, uint64_t max_rows, uint64_t ma
     slots[i] = seal_slot_bytes(lens[i]);
   }
   return plan_slots(n, slots.data(), max_rows, max_bytes, set_out, off_out);
+}
+
+Sets cut_sets(const std::vector<uint32_t>& set, const std::vector<uint64_t>& off, const std::vector<uint64_t>& slots) {
+  Sets s;
+  const size_t n = set.size();
+  for (size_t i = 0; i < n; ++i) {
+    if (i == 0 || set[i] != set[i - 1]) s.begin.push_back(i);
+    s.max_pool = std::max(s.max_pool, off[i] + slots[i]);
+  }
+  s.begin.push_back(n);
+  for (size_t k = 0; k + 1 < s.begin.size(); ++k) s.max_rows = std::max(s.max_rows, s.begin[k + 1] - s.begin[k]);
+  return s;
 }
 
 }  // namespace bmseal

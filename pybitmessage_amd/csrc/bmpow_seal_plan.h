@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 // Where the host puts a row's plaintext in its seal slot: the first multiple of 16 not below the longest
 // head (86 bytes), so the ciphertext written behind the head never reaches a block still to be read.
 constexpr uint32_t SL_PLAIN_AT = 96;
@@ -38,5 +40,34 @@ int64_t plan_slots(size_t n, const uint64_t* slots, uint64_t max_rows, uint64_t 
 // The same over plaintext lengths with seal_slot_bytes; a length above kMaxPlain is kPlanBadArg.
 int64_t plan_seal(size_t n, const uint64_t* lens, uint64_t max_rows, uint64_t max_bytes, uint32_t* set_out,
                   uint64_t* off_out);
+
+// The sets of a planned call: rows begin[k] .. begin[k + 1] are set k (begin ends at the number of rows), with
+// the largest set's rows and the largest pool, what a call's buffers are sized for once.
+struct Sets {
+  std::vector<size_t> begin;
+  uint64_t max_pool = 16;
+  size_t max_rows = 0;
+  size_t count() const { return begin.empty() ? 0 : begin.size() - 1; }
+};
+
+// From plan_slots' results: set[i], off[i] and the slots[i] it was given.
+Sets cut_sets(const std::vector<uint32_t>& set, const std::vector<uint64_t>& off, const std::vector<uint64_t>& slots);
+
+// A call's whole plan: the caller fills slot[], plan() lays the rows out and cuts the sets.
+struct SlotPlan {
+  std::vector<uint64_t> slot, off;
+  std::vector<uint32_t> set;
+  Sets sets;
+  bool plan(uint64_t max_rows, uint64_t max_bytes) {  // false where plan_slots refuses
+    off.resize(slot.size()), set.resize(slot.size());
+    if (plan_slots(slot.size(), slot.data(), max_rows, max_bytes, set.data(), off.data()) < 0) return false;
+    sets = cut_sets(set, off, slot);
+    return true;
+  }
+  uint64_t pool_bytes(size_t k) const {  // of set k
+    const size_t last = sets.begin[k + 1] - 1;
+    return off[last] + slot[last];
+  }
+};
 
 }  // namespace bmseal

@@ -1,7 +1,8 @@
 // bmpow_set_plan.h -- where a launch set ends (host only, no HIP: tests/native/setplan_sim.cpp builds it with
 // g++).  The receive-side host units send their rows, sorted by block count, through the device in sets of at
 // most max_objects rows and max_pool_bytes of 64-byte blocks; this is the one rule that cuts them.  Used by
-// bmpow_host_sig.hip, bmpow_host_rows.h (msgs and objects) and ecies_set_end (bmpow_host_ecies.hip).
+// bmpow_host_sig.hip, bmpow_host_rows.h (msgs and objects), ecies_set_end (bmpow_host_ecies.hip) and, for the
+// rows it does not seal, bmpow_host_send.hip.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

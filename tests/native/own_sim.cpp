@@ -2,10 +2,13 @@
 // for the HIP runtime (no GPU, no HIP): every allocation is released exactly once and on the device it
 // was made for, moves empty their source, grow() below the capacity allocates nothing, a failing grow()
 // leaves the owner empty, retiring (a move into a vector) releases nothing until the vector is cleared,
-// and with the exit flag set destructors release nothing.  Built with g++ under ASan + UBSan + LSan by
+// and with the exit flag set destructors release nothing.  The wiping owner (WipeBuf) on top: one zeroing
+// of the whole capacity on the owner's device right before each release, and none where nothing is
+// released.  Built with g++ under ASan + UBSan + LSan by
 // tests/test_native.py.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -30,6 +33,20 @@ struct Fake {
   static std::map<void*, int> live;
   static int allocs, frees, wrong_dev, unknown;
   static bool fail_next;
+  // the wiping owner's ledger: every zeroing (pointer, device, bytes) and the pointers freed, in order
+  struct Zero {
+    void* p;
+    int dev;
+    size_t bytes;
+  };
+  static std::vector<Zero> zeros;
+  static std::vector<void*> freed;
+  static int zero_not_live;
+  static void zero(int dev, void* p, size_t bytes) {
+    if (!live.count(p)) ++zero_not_live;  // zeroing after the free, or of a pointer never allocated
+    else std::memset(p, 0, bytes);        // the whole range is the allocation's (ASan)
+    zeros.push_back({p, dev, bytes});
+  }
   static err_t alloc(int dev, size_t bytes, unsigned, void** p, void** d) {
     if (fail_next) {
       fail_next = false;
@@ -49,15 +66,24 @@ struct Fake {
     if (it->second != dev) ++wrong_dev;
     live.erase(it);
     std::free(p);
+    freed.push_back(p);
     ++frees;
   }
-  static void reset_counts() { allocs = frees = wrong_dev = unknown = 0; }
+  static void reset_counts() {
+    allocs = frees = wrong_dev = unknown = zero_not_live = 0;
+    zeros.clear();
+    freed.clear();
+  }
 };
 std::map<void*, int> Fake::live;
 int Fake::allocs = 0, Fake::frees = 0, Fake::wrong_dev = 0, Fake::unknown = 0;
 bool Fake::fail_next = false;
+std::vector<Fake::Zero> Fake::zeros;
+std::vector<void*> Fake::freed;
+int Fake::zero_not_live = 0;
 
 using Buf = bmown::Buf<long, Fake>;
+using WBuf = bmown::WipeBuf<long, Fake>;
 
 struct Retirable {  // as the engine's launch buffers: several owners retired together
   Buf a, b;
@@ -173,6 +199,84 @@ void test_exit_flag() {
   }
 }
 
+// release number k (counted from 0) was of pointer p, and was preceded by exactly one zeroing: of p, on
+// device dev, of cap elements, while p was still live
+void wiped_before_free(size_t k, void* p, int dev, size_t cap) {
+  CHECK(Fake::freed.size() == k + 1 && Fake::zeros.size() == k + 1);
+  if (Fake::freed.size() != k + 1 || Fake::zeros.size() != k + 1) return;
+  CHECK(Fake::freed[k] == p);
+  CHECK(Fake::zeros[k].p == p && Fake::zeros[k].dev == dev && Fake::zeros[k].bytes == cap * sizeof(long));
+  CHECK(Fake::zero_not_live == 0);
+}
+
+void test_wipe_before_every_release() {
+  Fake::reset_counts();
+  {
+    WBuf x;
+    CHECK(x.alloc(3, 10) == Fake::ok);
+    x[9] = 7;
+    void* p = x.get();
+    x.reset();  // reset
+    wiped_before_free(0, p, 3, 10);
+    CHECK(x.alloc(4, 20) == Fake::ok);
+    p = x.get();
+    CHECK(x.alloc(5, 30) == Fake::ok);  // a second alloc
+    wiped_before_free(1, p, 4, 20);
+    p = x.get();
+    CHECK(x.grow(5, 31) == Fake::ok && x.cap() == 31);  // a grow that reallocates
+    wiped_before_free(2, p, 5, 30);
+    WBuf y;
+    CHECK(y.alloc(6, 8) == Fake::ok);
+    p = y.get();
+    void* q = x.get();
+    y = std::move(x);  // move-assignment over a live buffer: y's old one goes, x's is taken as it is
+    wiped_before_free(3, p, 6, 8);
+    CHECK(y.get() == q && y.cap() == 31 && y.dev() == 5 && !x);
+    p = q;
+    {
+      WBuf z(std::move(y));  // destruction, of the owner the buffer moved into
+      CHECK(Fake::zeros.size() == 4);
+    }
+    wiped_before_free(4, p, 5, 31);
+  }
+  CHECK(Fake::zeros.size() == 5 && Fake::frees == 5);  // the moved-from owners died without a zeroing
+  balanced();
+}
+
+void test_no_wipe_without_a_release() {
+  Fake::reset_counts();
+  {
+    WBuf empty;
+    empty.reset();  // an empty owner
+    WBuf x;
+    CHECK(x.grow(0, 16) == Fake::ok);
+    CHECK(x.grow(0, 16) == Fake::ok && x.grow(0, 3) == Fake::ok);  // a grow within the capacity
+    CHECK(Fake::zeros.empty() && Fake::frees == 0);
+    WBuf y(std::move(x));
+    x.reset();  // a moved-from owner
+    CHECK(Fake::zeros.empty() && Fake::frees == 0);
+    Fake::fail_next = true;
+    void* p = y.get();
+    CHECK(y.grow(0, 64) != Fake::ok && !y);  // a failing grow still released the old buffer: wiped first
+    wiped_before_free(0, p, 0, 16);
+  }
+  CHECK(Fake::zeros.size() == 1 && Fake::frees == 1);
+  balanced();
+  // after the exit flag: nothing is zeroed, nothing is freed
+  Fake::reset_counts();
+  void* leaked = nullptr;
+  {
+    WBuf x;
+    CHECK(x.alloc(2, 4) == Fake::ok);
+    leaked = x.get();
+    bmown::g_exiting.store(true);
+  }
+  CHECK(Fake::zeros.empty() && Fake::frees == 0 && Fake::live.size() == 1);
+  bmown::g_exiting.store(false);
+  Fake::live.erase(leaked);
+  std::free(leaked);
+}
+
 }  // namespace
 
 int main() {
@@ -181,6 +285,8 @@ int main() {
   test_grow();
   test_retire();
   test_exit_flag();
+  test_wipe_before_every_release();
+  test_no_wipe_without_a_release();
   if (g_failed) {
     std::fprintf(stderr, "%d checks failed\n", g_failed);
     return 1;

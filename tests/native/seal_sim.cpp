@@ -1,11 +1,12 @@
 // seal_sim.cpp -- the seal kernels' per-row code (pybitmessage_amd/csrc/bmpow_seal_rows.h, aes256_dev.h,
-// sha256_dev.h) and the set planner (bmpow_seal_plan.cpp) on the host, as a stand-alone program:
+// sha256_dev.h) and the set planner with its set cutter (bmpow_seal_plan.cpp) on the host, as a stand-alone program:
 // tests/test_seal.py builds it with g++ under AddressSanitizer + UBSan and runs it.  Every row works in a
 // heap slot of exactly the size the planner gives it, so a byte written or read past the slot is an error;
 // the results are compared with libcrypto's EVP calls.  Loads neither HIP nor the library.
 #include <openssl/evp.h>
 #include <openssl/hmac.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -273,6 +274,64 @@ static void test_plan() {
   CHECK(bmseal::plan_slots(1, &odd, R, B, set.data(), off.data()) == bmseal::kPlanBadArg, "slot no multiple of 16");
 }
 
+// cut_sets over plan_slots at limits of max_rows rows and max_bytes: begin[] strictly increasing and ending at
+// n, one set index per set, and max_rows / max_pool against a naive recomputation
+static void check_cut(const std::vector<uint64_t>& slots, uint64_t max_rows, uint64_t max_bytes) {
+  const size_t n = slots.size();
+  std::vector<uint32_t> set(n);
+  std::vector<uint64_t> off(n);
+  CHECK(bmseal::plan_slots(n, slots.data(), max_rows, max_bytes, set.data(), off.data()) >= 0, "plan refused (n %zu)", n);
+  const bmseal::Sets s = bmseal::cut_sets(set, off, slots);
+  CHECK(!s.begin.empty() && s.begin.back() == n && s.begin.front() == 0, "begin[] ends (n %zu)", n);
+  CHECK(s.count() == (n ? (size_t)set[n - 1] + 1 : 0), "set count %zu (n %zu)", s.count(), n);
+  size_t want_rows = 0;
+  uint64_t want_pool = 16;
+  for (size_t k = 0; k + 1 < s.begin.size(); ++k) {
+    const size_t i0 = s.begin[k], i1 = s.begin[k + 1];
+    CHECK(i0 < i1 && i1 <= n, "begin[] strictly increasing at set %zu", k);
+    if (!(i0 < i1 && i1 <= n)) return;
+    uint64_t pool = 0;
+    for (size_t i = i0; i < i1; ++i) {
+      CHECK(set[i] == set[i0], "rows of set %zu share one index", k);
+      pool += slots[i];
+    }
+    CHECK(i1 == n || set[i1] != set[i0], "set %zu ends where the index changes", k);
+    want_rows = std::max(want_rows, i1 - i0);
+    want_pool = std::max(want_pool, pool);
+  }
+  CHECK(s.max_rows == want_rows, "max_rows %zu, naive %zu (n %zu)", s.max_rows, want_rows, n);
+  CHECK(s.max_pool == want_pool, "max_pool %llu, naive %llu (n %zu)", (unsigned long long)s.max_pool,
+        (unsigned long long)want_pool, n);
+  // the same plan through SlotPlan
+  bmseal::SlotPlan p;
+  p.slot = slots;
+  CHECK(p.plan(max_rows, max_bytes) && p.sets.begin == s.begin && p.sets.max_pool == s.max_pool, "SlotPlan (n %zu)", n);
+  for (size_t k = 0; k < p.sets.count(); ++k) {
+    uint64_t pool = 0;
+    for (size_t i = s.begin[k]; i < s.begin[k + 1]; ++i) pool += slots[i];
+    CHECK(p.pool_bytes(k) == pool, "pool_bytes of set %zu", k);
+  }
+}
+
+static void test_cut_sets() {
+  const uint64_t R = 4, B = 64;  // tiny limits: 4 rows / 64 bytes
+  check_cut({}, R, B);
+  check_cut({16}, R, B);
+  check_cut({16, 16, 16, 16}, R, B);      // exactly one set, by rows and by bytes
+  check_cut({16, 16, 16, 16, 16}, R, B);  // one row over
+  check_cut({32, 32}, R, B);              // exactly one set by bytes
+  check_cut({32, 32, 16}, R, B);          // 16 bytes over
+  check_cut({0, 0, 0, 0, 0}, R, B);       // empty slots still count as rows
+  check_cut({80, 16, 16}, R, B);          // a row alone above the byte limit
+  check_cut({16, 80, 16}, R, B);
+  std::mt19937_64 rng(20261021);
+  for (int t = 0; t < 1000; ++t) {
+    std::vector<uint64_t> slots(rng() % 24);
+    for (auto& s : slots) s = 16 * (rng() % 6);  // 0 .. 80: some alone above the limit
+    check_cut(slots, R, B);
+  }
+}
+
 int main() {
   aes::fill_enc(g_enc, 0, 1);
   aes::fill_dec(g_dec, 0, 1);
@@ -281,6 +340,7 @@ int main() {
   test_cbc(rng);
   test_seal(rng);
   test_plan();
+  test_cut_sets();
   if (g_fail) return 1;
   std::fprintf(stderr, "all seal checks passed\n");
   return 0;

@@ -251,6 +251,49 @@ def test_two_sets_in_one_call(gpulib, pool):
         assert all(g == pubs[j] for g in got[j::128]), j
 
 
+def test_counters_of_every_kind_of_call(gpulib, pool, recipients):
+    """Three rows per call: calls, sets, rows and launches as the set loop counts them for a signature over
+    messages (hash, comb, sign), over digests (comb, sign), and an encryption (comb, digits, prep, shared)
+    sealed by the host, by the device, and -- one row above the device's limit -- by both, which is two trips
+    through the loop but one call.  The phase times add up to something, and hash_ms is exactly 0 where nothing
+    is hashed: the gap between the two events around a hash that was not launched is no hashing time."""
+    ks, pubs = pool
+    privs = [b32(k) for k in ks[:3]]
+    eph = [b32(k) for k in ks[3:6]]
+    ivs = [bytes([i]) * 16 for i in range(3)]
+    to = recipients[1][:3]
+    plains = [b'counted %d' % i for i in range(3)]
+    big = [plains[0], bytes((256 << 10) + 1), plains[2]]
+
+    def counted(call, seal=None):
+        prev = sender.set_seal(seal) if seal is not None else None
+        sender.reset_stats()
+        sender.reset_seal_stats()
+        try:
+            assert all(r is not None for r in call())
+        finally:
+            if prev is not None:
+                sender.set_seal(prev)
+        st = sender.stats()
+        print({k: st[k] for k in ('calls', 'sets', 'rows', 'launches', 'hash_ms', 'comb_ms', 'scalar_ms', 'ladder_ms')})
+        assert st['hash_ms'] + st['comb_ms'] + st['scalar_ms'] + st['ladder_ms'] > 0
+        return st, sender.seal_stats()
+
+    st, _ = counted(lambda: sender.sign_batch(plains, privs, 'sha256', nonces=eph))
+    assert (st['calls'], st['sets'], st['rows'], st['launches']) == (1, 1, 3, 3) and st['hash_ms'] > 0
+    st, _ = counted(lambda: sender.sign_digest(privs, eph, [hashlib.sha256(p).digest() for p in plains]))
+    assert (st['calls'], st['sets'], st['rows'], st['launches']) == (1, 1, 3, 2) and st['hash_ms'] == 0
+    st, seal = counted(lambda: sender.encrypt_batch(plains, to, ephemeral=eph, ivs=ivs), seal=0)
+    assert (st['calls'], st['sets'], st['rows'], st['launches']) == (1, 1, 3, 4) and st['hash_ms'] == 0
+    assert seal['launches'] == 0 and seal['rows_device'] == 0
+    st, seal = counted(lambda: sender.encrypt_batch(plains, to, ephemeral=eph, ivs=ivs), seal=1)
+    assert (st['calls'], st['sets'], st['rows'], st['launches']) == (1, 1, 3, 4) and st['hash_ms'] == 0
+    assert seal['launches'] == 1 and seal['rows_device'] == 3
+    st, seal = counted(lambda: sender.encrypt_batch(big, to, ephemeral=eph, ivs=ivs), seal=1)
+    assert (st['calls'], st['sets'], st['rows'], st['launches']) == (1, 2, 3, 8) and st['hash_ms'] == 0
+    assert seal['rows_device'] == 2 and seal['rows_host'] == 1
+
+
 def test_abort_is_honoured(gpulib, pool, recipients):
     ks, pubs = pool
     gpulib.bmpow_abort()

@@ -1,13 +1,16 @@
 """The send side, the parts that need no device: the ABI table of ``include/bmpow_send.h``,
 ``bmpow_sig_der`` against the oracle's encoder and back through ``bmpow_sig_parse``, ``bmpow_ecies_seal``
 against every blob the reference made (``tests/golden/send_kats.json``, tests/golden/make_send_golden.py)
-with the key derived by the integer oracle, the fixture's signatures against the oracle, and
-``worker.msg_plaintext`` against the fixture layout ``signatures.msg_signed_parts`` reads."""
+with the key derived by the integer oracle, the fixture's signatures against the oracle,
+``worker.msg_plaintext`` against the fixture layout ``signatures.msg_signed_parts`` reads, and the host
+units' scalar and byte toolkit as a stand-alone program under the sanitizers
+(tests/native/hostscalar_sim.cpp)."""
 import ctypes
 import hashlib
 import itertools
 import re
 import os
+import subprocess
 
 import pytest
 
@@ -144,3 +147,25 @@ def test_msg_plaintext_is_what_the_receive_side_reads(version):
     sig = b'\x30' + b'S' * 70
     signed, got_sig, key = signatures.msg_signed_parts(head, plain + worker._varint(len(sig)) + sig)
     assert signed == head[8:] + plain and got_sig == sig and key == pub_s
+
+
+def test_host_scalar_toolkit_under_sanitizers(tmp_path):
+    """pybitmessage_amd/csrc/bmpow_host_scalar.h built alone with g++ under AddressSanitizer + UBSan
+    (tests/native/hostscalar_sim.cpp), a stand-alone program that loads neither HIP nor the library: the
+    range checks at 0, 1, n - 1, n, n + 1, 2^256 - 1 and around p limb by limb, the byte conversions both
+    ways, the SHA padding into heap blocks of exactly msg_blocks(len) * 64 bytes, the DER encoder against
+    libcrypto's i2d_ECDSA_SIG and the strict parser, the parser on the encoder's outputs bent four ways, and
+    64 drawn scalars in range and distinct."""
+    csrc = os.path.join(ROOT, 'pybitmessage_amd', 'csrc')
+    exe = tmp_path / 'hostscalar_sim'
+    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Werror', '-Wno-unknown-pragmas',
+                           '-fsanitize=undefined,address', '-fno-sanitize-recover=all', '-static-libasan',
+                           '-static-libubsan', '-I', csrc, os.path.join(ROOT, 'tests', 'native', 'hostscalar_sim.cpp'),
+                           '-o', str(exe), '-lcrypto'])
+    env = dict(os.environ)
+    env['ASAN_OPTIONS'] = 'halt_on_error=1 detect_leaks=1'
+    env['UBSAN_OPTIONS'] = 'halt_on_error=1 print_stacktrace=1'
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert 'all host scalar checks passed' in r.stderr
+    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr

@@ -16,10 +16,15 @@ on a received msg (``ECDH_compute_key``, ``src/pyelliptic/ecc.py:243``):
   (``pybitmessage_amd/csrc/bmpow_sig.hip``): which 16-bit window of u1 meets plus or minus the
   accumulator, so a test can prove that a constructed case reaches the branch it was built for;
 * ``scalar_set``, ``comb_cases``, ``scalar_cases``, ``hash_cases`` -- the constructed families the CPU and
-  GPU tests share (seeded, built once per process).
+  GPU tests share (seeded, built once per process);
+* ``lift_x``, ``lift_y``, ``nearest``, ``key_for`` -- points chosen by a coordinate (an unknown discrete
+  logarithm) and the key under which a verification computes exactly a chosen R;
+* ``coordinate_points``, ``rn_cases``, ``rn_msg_cases``, ``key_cases``, ``ecdh_cases``, ``shared_cases``,
+  ``off_curve_points`` -- the families built from them (``tests/test_gpu_points.py``).
 
-Pinned by the reference-made fixtures ``tests/golden/sig_kats.json`` and ``tests/golden/ecies_kats.json``
-and by ``oracle/addrgen_oracle.py`` (``tests/test_ecdsa_oracle.py``) before anything is checked against it.
+Pinned by the reference-made fixtures ``tests/golden/sig_kats.json``, ``tests/golden/ecies_kats.json`` and
+``tests/golden/point_kats.json`` and by ``oracle/addrgen_oracle.py`` (``tests/test_ecdsa_oracle.py``,
+``tests/test_point_oracle.py``) before anything is checked against it.
 A ``mult_g`` costs about 0.1 ms, a ``mult`` about 1.5 ms.
 """
 import collections
@@ -418,4 +423,233 @@ def hash_cases():
         out.append(HashCase('len%d' % ln, msg, sig, pubs[j % 4], verify(msg, sig, pubs[j % 4])))
         bad = msg[:-1] + bytes([msg[-1] ^ 1]) if msg else b'\x00'
         out.append(HashCase('len%d_changed' % ln, bad, sig, pubs[j % 4], verify(bad, sig, pubs[j % 4])))
+    return tuple(out)
+
+
+# ------------------------------------------------------------------ points chosen by their coordinates
+# Every point above is m G for a known m.  The ones below are chosen by x or y instead (an unknown
+# discrete logarithm): p = 3 (mod 4) and p = 7 (mod 9), so a square root is a^((p + 1) / 4) and a cube
+# root a^((p + 2) / 9), one exponentiation each.
+def lift_x(x):
+    """The point (x, y) of the curve with the even y, or None where x is no coordinate of one."""
+    if not 0 <= x < P:
+        return None
+    a = (x * x * x + 7) % P
+    y = pow(a, (P + 1) // 4, P)
+    if y * y % P != a:
+        return None
+    return x, (P - y if y & 1 else y)
+
+
+def lift_y(y):
+    """A point (x, y) of the curve (one of the three with this y), or None where there is none."""
+    if not 0 <= y < P:
+        return None
+    a = (y * y - 7) % P
+    x = pow(a, (P + 2) // 9, P)
+    return (x, y) if x * x * x % P == a else None
+
+
+def nearest(start, step=1, by='x'):
+    """The first point of the curve whose x (or y) is ``start``, ``start + step``, ...; step is 1 or -1."""
+    assert step in (1, -1) and by in ('x', 'y')
+    lift = lift_x if by == 'x' else lift_y
+    v = start
+    while 0 <= v < P:
+        pt = lift(v)
+        if pt is not None:
+            return pt
+        v += step
+    raise ValueError('no point from %x on' % start)
+
+
+def _run_of(start, step, count, by='x'):
+    """``count`` successive points from ``start`` on, in the direction of ``step``."""
+    out, i = [], 0 if by == 'x' else 1
+    for _ in range(count):
+        out.append(nearest(start, step, by))
+        start = out[-1][i] + step
+    return out
+
+
+def key_for(R, r, s, e):
+    """The key Q for which the verification of (r, s) over e computes exactly R:
+    u1 G + u2 Q = R for u1 = e / s, u2 = r / s, so Q = (R - u1 G) / u2."""
+    assert 1 <= r < N and 1 <= s < N and on_curve(R)
+    w = pow(s, -1, N)
+    D = add(R, neg(mult_g(e % N * w % N)))
+    assert D is not None
+    return mult(pow(r * w % N, -1, N), D)
+
+
+X_EDGE = 2 ** 32 + 977  # 2^256 - p: x + p still fits 256 bits below it
+Y_ZERO_BYTES = (1, 8, 16, 31)
+X_ZERO_BYTES = (1, 2, 4, 8, 15, 16, 24, 31)
+
+
+@functools.lru_cache(maxsize=None)
+def coordinate_points():
+    """(name, point) for about 80 points chosen by a coordinate: next to 0, next to p, in [n, p), around
+    2^32 + 977, with z leading zero bytes, around 2^224 and 2^255; every fourth one also negated."""
+    rng = random.Random(1701)
+    out = []
+
+    def put(name, pts):
+        out.extend(('%s_%d' % (name, j), pt) for j, pt in enumerate(pts))
+
+    put('x_small', _run_of(1, 1, 8))
+    put('x_large', _run_of(P - 1, -1, 8))
+    put('x_from_n', _run_of(N + 1, 1, 4))
+    put('x_in_n_p', [nearest(rng.randrange(N, P)) for _ in range(4)])
+    put('x_below_edge', _run_of(X_EDGE - 1, -1, 2))
+    put('x_above_edge', _run_of(X_EDGE, 1, 2))
+    for z in X_ZERO_BYTES:
+        put('x_zero_bytes_%d' % z, [nearest(2 ** (8 * (32 - z) - 1))])
+    put('x_from_2_224', [nearest(2 ** 224)])
+    put('x_from_2_255', [nearest(2 ** 255)])
+    put('x_below_2_255', [nearest(2 ** 255 - 1, -1)])
+    put('y_small', _run_of(1, 1, 8, 'y'))
+    put('y_large', _run_of(P - 1, -1, 8, 'y'))
+    put('y_from_n', _run_of(N, 1, 4, 'y'))
+    for z in Y_ZERO_BYTES:
+        put('y_zero_bytes_%d' % z, [nearest(2 ** (8 * (32 - z) - 1), 1, 'y')])
+    full, base = [], {pt for _, pt in out}
+    for j, (name, pt) in enumerate(out):
+        full.append((name, pt))
+        if j % 4 == 0 and neg(pt) not in base:  # -(x, p - y) for a small y is already there, by its y
+            full.append((name + '_neg', neg(pt)))
+    assert all(on_curve(pt) for _, pt in full)
+    return tuple(full)
+
+
+def off_curve_points():
+    """(name, (x, y + 1)) for 8 of the points: off the curve, to be refused."""
+    pts = coordinate_points()
+    out = [(name + '_off', (pt[0], (pt[1] + 1) % P)) for name, pt in pts[::len(pts) // 8][:8]]
+    assert len(out) == 8 and not any(on_curve(pt) for _, pt in out)
+    return out
+
+
+RnCase = collections.namedtuple('RnCase', 'name family role R Q r s e valid')
+RnMsgCase = collections.namedtuple('RnMsgCase', 'name family R msg alg sig key code')
+RN_FAMILIES = ('x_above_n', 'rn_reaches_p', 'rn_carries')
+RN_MSG_ROWS = 8
+
+
+def _rn_points():
+    """Per family the points R (x(R) is what the family is about) and the r it pairs with x."""
+    rng = random.Random(1702)
+    above = _run_of(N + 1, 1, 8) + _run_of(P - 1, -1, 8) + [nearest(rng.randrange(N + 1, P)) for _ in range(8)]
+    reaches = _run_of(1, 1, 6) + _run_of(X_EDGE - 1, -1, 5) + [nearest(rng.randrange(1, X_EDGE - 64)) for _ in range(5)]
+    carries = (_run_of(1, 1, 6) + _run_of(X_EDGE - 1, -1, 2) + _run_of(X_EDGE, 1, 2)
+               + [nearest(rng.randrange(2 ** 254, 2 ** 255)) for _ in range(6)])
+    return (('x_above_n', above, lambda x: x - N), ('rn_reaches_p', reaches, lambda x: x + P - N),
+            ('rn_carries', carries, lambda x: x + 2 ** 256 - N))
+
+
+@functools.lru_cache(maxsize=None)
+def _rn_all():
+    rng = random.Random(1703)
+    V = _scalar_set()
+    digest, message = [], []
+    for family, points, r_of in _rn_points():
+        honest = family == 'x_above_n'
+        for j, R in enumerate(points):
+            if j % 2:
+                R = neg(R)
+            r, s, e = r_of(R[0]), V[rng.randrange(len(V))], rng.getrandbits(256)
+            name = '%s_%d' % (family, j)
+
+            Q = key_for(R, r, s, e)  # the verification of (r, s) over e computes exactly R
+
+            def row(role, Q, r, e):
+                return RnCase(name + ('' if role == 'row' else '_' + role), family, role, R, Q, r, s, e,
+                              verify_digest(Q, r, s, e))
+            digest.append(row('row', Q, r, e))
+            if honest:
+                digest.append(row('mutant_r', Q, r + 1, e))
+                digest.append(row('mutant_e', Q, r, e ^ 1))
+            else:
+                digest.append(row('sibling', key_for(R, R[0], s, e), R[0], e))
+            if j >= RN_MSG_ROWS:
+                continue
+            msg = bytes(rng.getrandbits(8) for _ in range(rng.randrange(201)))
+            alg = ('sha1', 'sha256')[j % 2]
+            em = int.from_bytes(hashlib.new(alg, msg).digest(), 'big')
+            key = xy_key(key_for(R, r, s, em))
+            sig = der_encode(r, s)
+            message.append(RnMsgCase(name + '_msg', family, R, msg, alg, sig, key, verify(msg, sig, key)))
+            if not honest:
+                key = xy_key(key_for(R, R[0], s, em))
+                sig = der_encode(R[0], s)
+                message.append(RnMsgCase(name + '_msg_sibling', family, R, msg, alg, sig, key, verify(msg, sig, key)))
+    return tuple(digest), tuple(message)
+
+
+def rn_cases():
+    """The second comparison of the kernel's ``x_is_r``, X = (r + n) Z^2, and its two guards.  Every row's
+    key is ``key_for`` its R, so the verification computes exactly R:
+
+    * 'x_above_n': n < x(R) < p and r = x - n: valid, by that comparison alone; per row the mutants
+      r + 1 and e ^ 1 (invalid);
+    * 'rn_reaches_p': x(R) < 2^32 + 977 and r = x + p - n: r + n = x + p fits 256 bits but is no canonical
+      field element; invalid;
+    * 'rn_carries': x(R) < 2 n - 2^256 and r = x + 2^256 - n: r + n leaves x in 256 bits; invalid;
+    * per invalid row the sibling with the same R, s and e and the honest r = x: valid.
+
+    ``valid`` is ``verify_digest``'s."""
+    return _rn_all()[0]
+
+
+def rn_msg_cases():
+    """The first ``RN_MSG_ROWS`` points of each family of ``rn_cases`` at message level: e is the SHA-1
+    (even rows) or SHA-256 (odd rows) digest of a seeded message of 0 to 200 bytes, the signature is DER;
+    ``code`` is ``verify``'s."""
+    return _rn_all()[1]
+
+
+KeyCase = collections.namedtuple('KeyCase', 'name family Q r s e valid')
+
+
+@functools.lru_cache(maxsize=None)
+def key_cases():
+    """Every point of ``coordinate_points`` as the key Q of a valid signature with seeded u1 and u2
+    (R = u1 G + u2 Q, r = x(R) mod n, s = r / u2, e = u1 s), and the mutant e + 1 (invalid)."""
+    rng = random.Random(1704)
+    out = []
+    for name, Q in coordinate_points():
+        u1, u2 = rng.randrange(1, N), rng.randrange(1, N)
+        r = add(mult_g(u1), mult(u2, Q))[0] % N
+        assert r
+        s = r * pow(u2, -1, N) % N
+        e = u1 * s % N
+        out.append(KeyCase(name, 'key', Q, r, s, e, verify_digest(Q, r, s, e)))
+        out.append(KeyCase(name + '_mutant', 'key_mutant', Q, r, s, e + 1, verify_digest(Q, r, s, e + 1)))
+    return tuple(out)
+
+
+EcdhCase = collections.namedtuple('EcdhCase', 'name k R x')
+ECDH_KEYS = 4
+
+
+@functools.lru_cache(maxsize=None)
+def ecdh_cases():
+    """Every point of ``coordinate_points`` as the other side's point R, with 4 keys of V: x(k R)."""
+    rng = random.Random(1705)
+    V = _scalar_set()
+    return tuple(EcdhCase('%s_k%d' % (name, j), k, R, mult(k, R)[0])
+                 for name, R in coordinate_points() for j, k in enumerate(rng.sample(V, ECDH_KEYS)))
+
+
+@functools.lru_cache(maxsize=None)
+def shared_cases():
+    """Every point of ``coordinate_points`` as the shared point S itself, with 4 keys of V: R = S / k, so
+    x(k R) = x(S)."""
+    rng = random.Random(1706)
+    V = _scalar_set()
+    out = []
+    for name, S in coordinate_points():
+        for j, k in enumerate(rng.sample(V, ECDH_KEYS)):
+            R = mult(pow(k, -1, N), S)
+            out.append(EcdhCase('%s_k%d' % (name, j), k, R, S[0]))
     return tuple(out)

@@ -207,17 +207,36 @@ def kernel_add(p, q, inf_branch, doubling):
     return x3, (rr * (v - x3) - y1 * hhh) % P, z1 * h % P, False
 
 
-def kernel_verdict(c, inf_branch=True, doubling='full'):
-    """``sg_comb_kernel`` for one digest: T = u2 Q, the comb over u1's windows, then X = r Z^2 or
-    (r + n) Z^2."""
+HAS_RN = ('as_is', 'never', 'no_carry_guard', 'no_canonical_guard')
+
+
+def kernel_point(c, inf_branch=True, doubling='full'):
+    """``sg_comb_kernel`` up to its comparison: T = u2 Q, then the comb over u1's windows; (X, Y, Z, inf)."""
     T = eo.mult(c.u2, c.case.Q)
     acc = (T[0], T[1], 1, False)
     for i, v in enumerate(eo.comb_windows(c.u1)):
         if v:
             acc = kernel_add(acc, comb_entry(i, v), inf_branch, doubling)
+    return acc
+
+
+def kernel_decide(acc, r, has_rn='as_is'):
+    """``x_is_r`` and the guard in front of it: X = r Z^2, or X = (r + n) Z^2 with r + n as the kernel holds
+    it, in 256 bits, which counts only when ``has_rn``: no carry out of 256 bits (``c == 0``) and already
+    canonical (``same == 0``), that is r + n < p.  ``has_rn`` 'never' drops the second comparison,
+    'no_carry_guard' and 'no_canonical_guard' one of its two guards."""
     x, _, z, inf = acc
-    r = c.case.r
-    return not inf and ((x - r * z * z) % P == 0 or (r + N < P and (x - (r + N) * z * z) % P == 0))
+    rn, carry = (r + N) % 2 ** 256, (r + N) >> 256
+    canonical = rn < P  # fe_normalize leaves it as it is
+    guard = {'as_is': not carry and canonical, 'never': False, 'no_carry_guard': canonical,
+             'no_canonical_guard': not carry}[has_rn]
+    return not inf and ((x - r * z * z) % P == 0 or (guard and (x - rn * z * z) % P == 0))
+
+
+def kernel_verdict(c, inf_branch=True, doubling='full', has_rn='as_is'):
+    """``sg_comb_kernel`` for one digest: T = u2 Q, the comb over u1's windows, then X = r Z^2 or
+    (r + n) Z^2."""
+    return kernel_decide(kernel_point(c, inf_branch, doubling), c.case.r, has_rn)
 
 
 def test_a_comb_without_a_branch_gets_constructed_cases_wrong():

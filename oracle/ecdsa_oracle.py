@@ -20,7 +20,10 @@ on a received msg (``ECDH_compute_key``, ``src/pyelliptic/ecc.py:243``):
 * ``lift_x``, ``lift_y``, ``nearest``, ``key_for`` -- points chosen by a coordinate (an unknown discrete
   logarithm) and the key under which a verification computes exactly a chosen R;
 * ``coordinate_points``, ``rn_cases``, ``rn_msg_cases``, ``key_cases``, ``ecdh_cases``, ``shared_cases``,
-  ``off_curve_points`` -- the families built from them (``tests/test_gpu_points.py``).
+  ``off_curve_points`` -- the families built from them (``tests/test_gpu_points.py``);
+* ``sign_cases``, ``len_grid``, ``s_len_values``, ``key_from_s``, ``SHORT_R_NONCES`` -- the signing side:
+  rows (d, k, e) whose k, 1 / k, d, e + r d, s, the integer sum the addition sees and the byte lengths of r
+  and s are chosen (``tests/test_sign_oracle.py``, ``tests/test_gpu_sign_constructed.py``).
 
 Pinned by the reference-made fixtures ``tests/golden/sig_kats.json``, ``tests/golden/ecies_kats.json`` and
 ``tests/golden/point_kats.json`` and by ``oracle/addrgen_oracle.py`` (``tests/test_ecdsa_oracle.py``,
@@ -423,6 +426,121 @@ def hash_cases():
         out.append(HashCase('len%d' % ln, msg, sig, pubs[j % 4], verify(msg, sig, pubs[j % 4])))
         bad = msg[:-1] + bytes([msg[-1] ^ 1]) if msg else b'\x00'
         out.append(HashCase('len%d_changed' % ln, bad, sig, pubs[j % 4], verify(bad, sig, pubs[j % 4])))
+    return tuple(out)
+
+
+# ------------------------------------------------------------------ signatures chosen by their r and s
+# s = (e + r d) / k: any s, any 1 / k and any e + r d is forced by solving for d or e; nothing is searched
+# but the nonces below, whose r = x(k G) is short.
+SignCase = collections.namedtuple('SignCase', 'name family d k e r s')
+ShortR = collections.namedtuple('ShortR', 'name k r_len top')  # r_len: the bytes of r without a pad; top: their top bit
+
+_WALK = 2 ** 128  # x((_WALK + j) G) for j = 0, 1, ... by one affine addition of G per step
+SHORT_R_NONCES = (
+    # 2 ((n + 1) / 2) G = G: the half of G, known for its x of 166 bits, 0x3b78ce563f89a0ed9414f5aa28ad0d96d6795f9c63
+    ShortR('half', (N + 1) // 2, 21, 0),
+    # the first j of the walk from 2^128 whose x has one (two) leading zero bytes and the next byte's top bit
+    # clear (set): found at the steps 478, 610, 18459 and 73225, 1.3 s of additions in all
+    ShortR('z1_clear', _WALK + 478, 31, 0),
+    ShortR('z1_set', _WALK + 610, 31, 1),
+    ShortR('z2_clear', _WALK + 18459, 30, 0),
+    ShortR('z2_set', _WALK + 73225, 30, 1),
+    # the first two steps of the same walk with a full-width x, top bit set and clear
+    ShortR('full_set', _WALK, 32, 1),
+    ShortR('full_clear', _WALK + 4, 32, 0),
+    # the ends of the range: x(G) = x(-G) has the top bit clear, x(2 G) = x(-2 G) has it set
+    ShortR('one', 1, 32, 0),
+    ShortR('two', 2, 32, 1),
+    ShortR('minus_one', N - 1, 32, 0),
+    ShortR('minus_two', N - 2, 32, 1),
+)
+SUM_EDGES = (N - 1, N, N + 1, 2 ** 256 - 1, 2 ** 256, 2 ** 256 + 1, 2 * N - 2)
+
+
+def s_len_values():
+    """The s of the length family: 2^(8 L - 1) (L bytes with the top bit set: a pad), 2^(8 L - 1) - 1 (L bytes,
+    no pad, every bit below set) and 2^(8 (L - 1)) (L bytes, the lowest value) for L = 1 .. 32 -- all below n,
+    96 values -- and n - 1, the largest s there is."""
+    out = []
+    for ln in range(1, 33):
+        out += [2 ** (8 * ln - 1), 2 ** (8 * ln - 1) - 1, 2 ** (8 * (ln - 1))]
+    out = [s for s in out if 1 <= s < N] + [N - 1]
+    assert len(set(out)) == len(out)
+    return out
+
+
+def key_from_s(k, s, e):
+    """(r, d): the key d that makes (r = x(k G) mod n, s) the signature of e under the nonce k,
+    d = (s k - e) / r."""
+    r = mult_g(k)[0] % N
+    assert r
+    return r, (s * k - e) * pow(r, -1, N) % N
+
+
+@functools.lru_cache(maxsize=None)
+def len_grid():
+    """(ShortR, r, s) for every nonce of SHORT_R_NONCES and every s of ``s_len_values``: what the length
+    family is made of, whatever the digest."""
+    return tuple((n, mult_g(n.k)[0] % N, s) for n in SHORT_R_NONCES for s in s_len_values())
+
+
+@functools.lru_cache(maxsize=None)
+def sign_cases():
+    """Signing rows (d, k, e) with the (r, s) signing must return (s = 0: the row is refused), V = scalar_set():
+
+    * 'k': k = v, the input of the inversion and the windows of the comb;
+    * 'kinv': k = 1 / v, so the inversion's output and the first operand of the last product is v;
+    * 'd': d = v, the second operand of r d;
+    * 't': e + r d = v (mod n), the second operand of the last product: e = v - r d mod n for a seeded d, and
+      (a seeded e is below 2^256 - n once in 2^127) a second row per v with a seeded e below 2^256 - n,
+      d = (v - e) / r and the digest given unreduced as e + n;
+    * 's': s = v, d = (s k - e) / r;
+    * 'sum': the integer T = (r d mod n) + (e mod n) the addition sees, at the SUM_EDGES and at 16 seeded T in
+      (n, 2^256) and 16 in (2^256, 2 n - 2): e is 5, n + 5 (unreduced) or n - 1, whichever leaves
+      1 <= T - (e mod n) < n, and d = (T - e mod n) / r; T = n is the row with s = 0;
+    * 'len': every pair of ``len_grid``, a seeded digest and d = (s k - e) / r: r and s of every byte length.
+
+    Everything not forced is seeded."""
+    rng = random.Random(1801)
+    V = _scalar_set()
+    out = []
+
+    def scalar():
+        return rng.randrange(1, N)
+
+    def put(name, family, d, k, e):
+        assert 1 <= d < N and 1 <= k < N and 0 <= e < 2 ** 256
+        r = mult_g(k)[0] % N
+        assert r
+        out.append(SignCase(name, family, d, k, e, r, (e + r * d) * pow(k, -1, N) % N))
+
+    for j, v in enumerate(V):
+        put('k_%d' % j, 'k', scalar(), v, rng.getrandbits(256))
+    for j, v in enumerate(V):
+        put('kinv_%d' % j, 'kinv', scalar(), pow(v, -1, N), rng.getrandbits(256))
+    for j, v in enumerate(V):
+        put('d_%d' % j, 'd', v, scalar(), rng.getrandbits(256))
+    top = 2 ** 256 - N
+    for j, v in enumerate(V):
+        k, d = scalar(), scalar()
+        r = mult_g(k)[0] % N
+        put('t_%d' % j, 't', d, k, (v - r * d) % N)
+        k, e = scalar(), rng.randrange(top)
+        r = mult_g(k)[0] % N
+        put('t_plus_n_%d' % j, 't', (v - e) * pow(r, -1, N) % N, k, e + N)
+    for j, v in enumerate(V):
+        k, e = scalar(), rng.getrandbits(256)
+        put('s_%d' % j, 's', key_from_s(k, v, e)[1], k, e)
+    sums = list(SUM_EDGES) + [rng.randrange(N + 1, 2 ** 256) for _ in range(16)]
+    sums += [rng.randrange(2 ** 256 + 1, 2 * N - 2) for _ in range(16)]
+    for j, T in enumerate(sums):
+        e = next(e for e in ((5, N + 5)[j % 2], N - 1) if 1 <= T - e % N < N)
+        k = scalar()
+        r = mult_g(k)[0] % N
+        put('sum_%d' % j, 'sum', (T - e % N) * pow(r, -1, N) % N, k, e)
+    for j, (nonce, r, s) in enumerate(len_grid()):
+        e = rng.getrandbits(256)
+        put('len_%s_%d' % (nonce.name, j % len(s_len_values())), 'len', key_from_s(nonce.k, s, e)[1], nonce.k, e)
     return tuple(out)
 
 

@@ -74,28 +74,6 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_comb_kernel(const ge* __restrict_
   pt[o] = r;
 }
 
-// r = a + b mod n for a, b < n
-BM_DEV void sc_add(sc& r, const sc& a, const sc& b) {
-  uint32_t t[8], u[8];
-  uint64_t c = 0, bw = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += (uint64_t)a.d[i] + b.d[i];
-    t[i] = (uint32_t)c;
-    c >>= 32;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint64_t v = (uint64_t)t[i] - sn::N(i) - bw;
-    u[i] = (uint32_t)v;
-    bw = (v >> 32) & 1u;
-  }
-  // a + b < 2 n < 2^257: with a carry out of 256 bits the sum is above n and t - n wraps to it
-  const bool sub = c != 0 || bw == 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.d[i] = sub ? u[i] : t[i];
-}
-
 __global__ __launch_bounds__(SD_BLOCK) void sd_sign_kernel(const ge* __restrict__ pt, const sg_kw* __restrict__ kw,
                                                            const sc* __restrict__ d, const sc* __restrict__ e,
                                                            uint32_t n, uint32_t stride, sc* __restrict__ rs,
@@ -112,7 +90,7 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_sign_kernel(const ge* __restrict_
   sn::set(one, 1);
   sn::mul(em, e[o], one);  // e mod n
   sn::mul(t, r, d[o]);
-  sc_add(t, t, em);
+  sn::add(t, t, em);
   sn::mul(s, ki, t);
   rs[o] = r;
   rs[(size_t)stride + o] = s;

@@ -90,6 +90,28 @@ SN_HD void neg(sc& r, const sc& a) {
   }
 }
 
+// r = a + b mod n for a, b < n
+SN_HD void add(sc& r, const sc& a, const sc& b) {
+  uint32_t t[8], u[8];
+  uint64_t c = 0, bw = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c += (uint64_t)a.d[i] + b.d[i];
+    t[i] = (uint32_t)c;
+    c >>= 32;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t v = (uint64_t)t[i] - N(i) - bw;
+    u[i] = (uint32_t)v;
+    bw = (v >> 32) & 1u;
+  }
+  // a + b < 2 n < 2^257: with a carry out of 256 bits the sum is above n and t - n wraps to it
+  const bool sub = c != 0 || bw == 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r.d[i] = sub ? u[i] : t[i];
+}
+
 // o[0 .. ON) = lo[0 .. 8) + hi[0 .. HN) * c; the caller's bound on the value fits ON limbs
 template <int HN, int ON>
 SN_HD void fold(uint32_t (&o)[ON], const uint32_t* lo, const uint32_t* hi) {

@@ -6,6 +6,7 @@
 // OPERANDS holds one operation per line, numbers as 64 hex digits:
 //   mul A B   -> A B mod n
 //   inv A     -> A^-1 mod n
+//   add A B   -> A + B mod n (A, B < n)
 //   rec U     -> U made odd and recoded (0 < U < n): the flip flag and the 64 digits, least significant first
 // One line of output per line of input.
 #include <cstdio>
@@ -41,6 +42,10 @@ int main(int argc, char** argv) {
     if (!std::strcmp(op, "mul")) {
       if (got != 3 || !parse(y, b)) return 3;
       sn::mul(r, a, b);
+      print(r);
+    } else if (!std::strcmp(op, "add")) {
+      if (got != 3 || !parse(y, b)) return 3;
+      sn::add(r, a, b);
       print(r);
     } else if (!std::strcmp(op, "inv")) {
       sn::inv(r, a);

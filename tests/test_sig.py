@@ -11,7 +11,7 @@ import subprocess
 
 import pytest
 
-from oracle.ecdsa_oracle import der_decode
+from oracle.ecdsa_oracle import der_decode, scalar_set, sign_cases
 from pybitmessage_amd import _lib, signatures
 from tests.conftest import ROOT
 
@@ -156,10 +156,18 @@ def test_scalar_products_and_inverses(scalar_sim):
     ops += [('mul', a, rng.choice(edge + rand + unreduced)) for a in edge + rand + unreduced]
     ops += [('inv', a) for a in edge + rand[:600]]
     ops += [('inv', a) for a in unreduced if a % N]
+    # sn::add (the signing kernel's e + r d): V x V, and the operand pairs of the oracle's 'sum' family, whose
+    # integer sums lie at n, at 2^256 and at 2 n - 2
+    V = scalar_set()
+    sums = [(c.r * c.d % N, c.e % N) for c in sign_cases() if c.family == 'sum']
+    assert len(V) == 735 and len(sums) == 39
+    assert {N - 1, N, N + 1, 2 ** 256 - 1, 2 ** 256, 2 ** 256 + 1, 2 * N - 2} <= {a + b for a, b in sums}
+    ops += [('add', a, b) for a in V for b in V]
+    ops += [('add', a, b) for a, b in sums] + [('add', b, a) for a, b in sums]
     out = scalar_sim(ops)
     bad = []
     for (op, *v), line in zip(ops, out):
-        want = v[0] * v[1] % N if op == 'mul' else pow(v[0], -1, N)
+        want = v[0] * v[1] % N if op == 'mul' else (v[0] + v[1]) % N if op == 'add' else pow(v[0], -1, N)
         if int(line, 16) != want:
             bad.append((op, [hex(x) for x in v], line))
     assert not bad, bad[:3]

@@ -434,6 +434,45 @@ TX_SIGNATURES = [
     ('bmpow_tx_reset_stats', None, []),
 ]
 
+class BmpowPacketRec(ctypes.Structure):
+    """``bmpow_packet_rec`` (include/bmpow_packets.h): one framed packet, 120 bytes."""
+    _fields_ = [('conn', ctypes.c_uint32), ('offset', ctypes.c_uint32), ('length', ctypes.c_uint32),
+                ('command', ctypes.c_uint8), ('exact', ctypes.c_uint8), ('reserved', ctypes.c_uint16),
+                ('checksum', ctypes.c_uint32), ('computed', ctypes.c_uint32), ('status', ctypes.c_uint32),
+                ('reserved2', ctypes.c_uint32), ('intake', BmpowIntakeRec)]
+
+
+class BmpowPacketConn(ctypes.Structure):
+    """``bmpow_packet_conn`` (include/bmpow_packets.h): where one connection's walk stands."""
+    _fields_ = [('consumed', ctypes.c_uint64), ('first', ctypes.c_uint32), ('count', ctypes.c_uint32),
+                ('close', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+class BmpowPacketsStats(ctypes.Structure):
+    """``bmpow_packets_stats`` (include/bmpow_packets.h)."""
+    _fields_ = [('calls', ctypes.c_uint64), ('packets', ctypes.c_uint64), ('object_rows', ctypes.c_uint64),
+                ('sum_rows', ctypes.c_uint64), ('host_rows', ctypes.c_uint64), ('empty_rows', ctypes.c_uint64),
+                ('blocks', ctypes.c_uint64), ('pack_ms', ctypes.c_double), ('object_ms', ctypes.c_double),
+                ('sum_ms', ctypes.c_double), ('host_frame_ms', ctypes.c_double), ('host_build_ms', ctypes.c_double),
+                ('host_run_ms', ctypes.c_double), ('host_status_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_packets.h declares
+PACKETS_SIGNATURES = [
+    ('bmpow_packets_frame', ctypes.c_int64,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.POINTER(BmpowPacketConn)]),
+    ('bmpow_packets_count', ctypes.c_int64, [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p]),
+    ('bmpow_packets_row_blocks', ctypes.c_uint32, [ctypes.c_int, ctypes.c_uint64]),
+    ('bmpow_packets_batch', ctypes.c_int64,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p, ctypes.POINTER(BmpowIntakeParams), ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
+    ('bmpow_packets_ack_batch', ctypes.c_int,
+     [ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.POINTER(BmpowIntakeParams), ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_packets_get_stats', ctypes.c_int, [ctypes.POINTER(BmpowPacketsStats)]),
+    ('bmpow_packets_reset_stats', None, []),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -453,7 +492,7 @@ def load(path=None):
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
                             SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES +
-                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES):
+                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES + PACKETS_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

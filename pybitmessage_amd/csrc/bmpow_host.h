@@ -224,5 +224,6 @@ void probe_release_shards();
 void verify_release_shards();
 void addr_release_shards();
 void intake_release_shards();
+void packets_release_shards();
 
 }  // namespace bmhost

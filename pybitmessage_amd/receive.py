@@ -425,7 +425,8 @@ def sealed_reset_stats():
 def ack_has_valid_header(ackData):
     """``objectProcessor.ackDataHasAValidHeader`` (``src/class_objectProcessor.py:1020-1054``), on the host:
     whether a msg's ackData is one well-formed ``object`` packet, which is what ``:725-731`` asks before the
-    acknowledgement is sent on."""
+    acknowledgement is sent on.  One ack at a time, with hashlib; :func:`pybitmessage_amd.packets.check_acks` is
+    the same answer for a batch in one device call, and :func:`check_opened_acks` feeds it a batch's acks."""
     ackData = bytes(ackData)
     if len(ackData) < 24:
         return False
@@ -438,6 +439,17 @@ def ack_has_valid_header(ackData):
     if checksum != hashlib.sha512(payload).digest()[:4]:
         return False
     return command.rstrip(b'\x00') == b'object'
+
+
+def check_opened_acks(opened, **intake_parameters):
+    """The acknowledgements of a batch's accepted rows through :func:`pybitmessage_amd.packets.check_acks` in one
+    call: ``(rows, valid, IntakeResult)`` with ``rows`` = ``opened.accepted()`` (an :class:`OpenedMsgs`), ``valid[j]``
+    what ``ackDataHasAValidHeader`` says to row ``rows[j]``'s ackData, and the intake record of the object it
+    carries: what ``bm_command_object`` will find when the ack is sent on (``:725-731``)."""
+    from . import packets
+    rows = opened.accepted()
+    valid, res = packets.check_acks([opened.ackData(i) for i in rows], **intake_parameters)
+    return rows, valid, res
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -473,6 +473,51 @@ PACKETS_SIGNATURES = [
     ('bmpow_packets_reset_stats', None, []),
 ]
 
+
+class BmpowInvValue(ctypes.Structure):
+    """``bmpow_inv_value`` (include/bmpow_inv.h): what a set keeps beside a key."""
+    _fields_ = [('expires', ctypes.c_uint64), ('stream', ctypes.c_uint32), ('aux', ctypes.c_uint32)]
+
+
+class BmpowInvPkt(ctypes.Structure):
+    """``bmpow_inv_pkt`` (include/bmpow_inv.h): one ``inv`` / ``dinv`` / ``getdata`` payload as walked."""
+    _fields_ = [('count', ctypes.c_uint64), ('first_item', ctypes.c_uint32), ('n_items', ctypes.c_uint32),
+                ('item_offset', ctypes.c_uint32), ('status', ctypes.c_int32)]
+
+
+class BmpowInvStats(ctypes.Structure):
+    """``bmpow_inv_stats`` (include/bmpow_inv.h)."""
+    _fields_ = [('slots', ctypes.c_uint64), ('seed', ctypes.c_uint64), ('live', ctypes.c_uint64),
+                ('tombstones', ctypes.c_uint64), ('calls', ctypes.c_uint64), ('rows', ctypes.c_uint64),
+                ('launches', ctypes.c_uint64), ('rebuilds', ctypes.c_uint64), ('probes', ctypes.c_uint64),
+                ('longest_probe', ctypes.c_uint64), ('lookup_ms', ctypes.c_double), ('claim_ms', ctypes.c_double),
+                ('finalize_ms', ctypes.c_double), ('bury_ms', ctypes.c_double), ('rebuild_ms', ctypes.c_double),
+                ('list_ms', ctypes.c_double), ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_inv.h declares
+INV_SIGNATURES = [
+    ('bmpow_invset_create', _vp, [_u64, _u64]),
+    ('bmpow_invset_destroy', None, [_vp]),
+    ('bmpow_invset_clear', ctypes.c_int, [_vp]),
+    ('bmpow_invset_len', ctypes.c_int64, [_vp]),
+    ('bmpow_invset_stats', ctypes.c_int, [_vp, ctypes.POINTER(BmpowInvStats)]),
+    ('bmpow_invset_add', ctypes.c_int,
+     [_vp, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ('bmpow_invset_contains', ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_invset_remove', ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_invset_sweep', ctypes.c_int64, [_vp, _u64]),
+    ('bmpow_invset_list', ctypes.c_int64, [_vp, ctypes.c_uint32, _u64, ctypes.c_void_p, ctypes.c_size_t]),
+    ('bmpow_invset_slot', _u64, [_u64, ctypes.c_uint32, ctypes.c_char_p]),
+    ('bmpow_inv_walk', ctypes.c_int, [ctypes.c_void_p, _u64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BmpowInvPkt)]),
+    ('bmpow_inv_batch', ctypes.c_int64,
+     [_vp, _vp, ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p, _u64, ctypes.c_int, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    ('bmpow_inv_admit', ctypes.c_int,
+     [_vp, _vp, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -492,7 +537,7 @@ def load(path=None):
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
                             SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES +
-                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES + PACKETS_SIGNATURES):
+                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES + PACKETS_SIGNATURES + INV_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

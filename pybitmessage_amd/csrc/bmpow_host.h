@@ -225,5 +225,6 @@ void verify_release_shards();
 void addr_release_shards();
 void intake_release_shards();
 void packets_release_shards();
+void inv_release_shards();
 
 }  // namespace bmhost

@@ -6,8 +6,8 @@ The reference's network thread builds a ``BMObject`` for every received object
 runs the EOL, stream and per-type checks of ``src/network/bmobject.py:71-163``.  Here
 :func:`check_objects` does that for a list of objects with one upload and one launch per shard
 (``bmpow_intake_batch``, include/bmpow_intake.h), and :func:`inventory_hashes` gives the hashes
-alone.  The already-have lookup (``checkAlreadyHave``) stays with the caller, who gets the hash
-for it.  No CPU fallback: without the HIP library the calls raise :class:`BmpowUnavailable`.
+alone.  The already-have lookup (``checkAlreadyHave``) and the store behind it are
+:func:`pybitmessage_amd.inventory.admit`, which takes the :class:`IntakeResult` as it is.  No CPU fallback: without the HIP library the calls raise :class:`BmpowUnavailable`.
 """
 import ctypes
 

@@ -10,7 +10,9 @@ buffers as they came off the sockets with one upload and one pass over the devic
 packet the record :func:`pybitmessage_amd.intake.check_objects` would give for its payload -- the checksum
 comes out of the same hash chain as the inventory hash.  :func:`check_acks` is
 ``objectProcessor.ackDataHasAValidHeader`` for a batch of acknowledgements, and :func:`frame` the walk alone,
-on the host.  The handlers behind the packets (``inv``, ``addr``, ``version`` ...) stay with the caller.
+on the host.  The item lists of ``inv`` / ``dinv`` / ``getdata`` packets go on to
+:func:`pybitmessage_amd.inventory.check_invs`, which takes a :class:`PacketResult` as it is; the other handlers
+(``addr``, ``version`` ...) stay with the caller.
 No CPU fallback: without the HIP library the device calls raise :class:`BmpowUnavailable`.
 """
 import ctypes

@@ -518,6 +518,59 @@ INV_SIGNATURES = [
      [_vp, _vp, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 ]
 
+
+class BmpowProcRec(ctypes.Structure):
+    """``bmpow_proc_rec`` (include/bmpow_proc.h): one dispatched object, 72 bytes."""
+    _fields_ = [('version', ctypes.c_uint64), ('stream', ctypes.c_uint64), ('port', ctypes.c_uint64),
+                ('route', ctypes.c_uint32), ('ack', ctypes.c_uint32), ('ack_aux', ctypes.c_uint32),
+                ('ack_first', ctypes.c_uint32), ('status', ctypes.c_uint32), ('key_off', ctypes.c_uint32),
+                ('key_len', ctypes.c_uint32), ('address', ctypes.c_uint32), ('host_off', ctypes.c_uint32),
+                ('host_len', ctypes.c_uint32), ('host_class', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+class BmpowProcAddress(ctypes.Structure):
+    """``bmpow_proc_address`` (include/bmpow_proc.h): one of my addresses, 80 bytes."""
+    _fields_ = [('ripe', ctypes.c_uint8 * 20), ('tag', ctypes.c_uint8 * 32), ('version', ctypes.c_uint32),
+                ('stream', ctypes.c_uint64), ('last_pubkey_send_time', ctypes.c_int64), ('chan', ctypes.c_uint32),
+                ('reserved', ctypes.c_uint32)]
+
+
+class BmpowProcParams(ctypes.Structure):
+    """``bmpow_proc_params`` (include/bmpow_proc.h)."""
+    _fields_ = [('now', ctypes.c_int64), ('rows_per_launch', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
+class BmpowProcStats(ctypes.Structure):
+    """``bmpow_proc_stats`` (include/bmpow_proc.h)."""
+    _fields_ = [('seed', ctypes.c_uint64), ('watch_len', ctypes.c_uint64), ('watch_slots', ctypes.c_uint64),
+                ('watch_lengths', ctypes.c_uint64), ('addresses', ctypes.c_uint64), ('calls', ctypes.c_uint64),
+                ('rows', ctypes.c_uint64), ('rows_uploaded', ctypes.c_uint64), ('ack_rows', ctypes.c_uint64),
+                ('bytes_uploaded', ctypes.c_uint64), ('table_uploads', ctypes.c_uint64), ('launches', ctypes.c_uint64),
+                ('found', ctypes.c_uint64), ('rows_ms', ctypes.c_double), ('finish_ms', ctypes.c_double),
+                ('host_ms', ctypes.c_double)]
+
+
+# the same for every symbol include/bmpow_proc.h declares
+PROC_SIGNATURES = [
+    ('bmpow_proc_create', _vp, [_u64, ctypes.c_int]),
+    ('bmpow_proc_destroy', None, [_vp]),
+    ('bmpow_proc_stats_get', ctypes.c_int, [_vp, ctypes.POINTER(BmpowProcStats)]),
+    ('bmpow_proc_stats_reset', ctypes.c_int, [_vp]),
+    ('bmpow_proc_watch_add', ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_char_p, _p64, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_proc_watch_discard', ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_char_p, _p64, ctypes.c_void_p]),
+    ('bmpow_proc_watch_contains', ctypes.c_int,
+     [_vp, ctypes.c_size_t, ctypes.c_char_p, _p64, ctypes.c_void_p, ctypes.c_void_p]),
+    ('bmpow_proc_watch_len', ctypes.c_int64, [_vp]),
+    ('bmpow_proc_watch_clear', ctypes.c_int, [_vp]),
+    ('bmpow_proc_watch_slot', _u64, [_u64, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
+    ('bmpow_proc_set_addresses', ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_void_p]),
+    ('bmpow_proc_batch', ctypes.c_int,
+     [_vp, ctypes.c_size_t, ctypes.c_void_p, _p64, ctypes.c_void_p, ctypes.POINTER(BmpowProcParams), ctypes.c_void_p]),
+    ('bmpow_proc_walk', ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_char_p, _u64, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64,
+      ctypes.POINTER(BmpowProcRec)]),
+]
+
 _lock = threading.Lock()
 _lib = None
 _host = None
@@ -537,7 +590,8 @@ def load(path=None):
     lib = ctypes.CDLL(path)
     for name, res, args in (SIGNATURES + ECIES_SIGNATURES + INTAKE_SIGNATURES + SIG_SIGNATURES + SEND_SIGNATURES +
                             SEAL_SIGNATURES + IDENT_SIGNATURES + RX_SIGNATURES + RXOBJ_SIGNATURES + TX_SIGNATURES +
-                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES + PACKETS_SIGNATURES + INV_SIGNATURES):
+                            RXOPEN_SIGNATURES + RXOBJOPEN_SIGNATURES + PACKETS_SIGNATURES + INV_SIGNATURES +
+                            PROC_SIGNATURES):
         try:
             fn = getattr(lib, name)
         except AttributeError:

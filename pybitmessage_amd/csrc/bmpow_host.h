@@ -226,5 +226,6 @@ void addr_release_shards();
 void intake_release_shards();
 void packets_release_shards();
 void inv_release_shards();
+void proc_release_shards();
 
 }  // namespace bmhost

@@ -26,6 +26,7 @@
 //   bmpow_host_intake.hip  object intake: inventory hashes, header walk and checks (include/bmpow_intake.h)
 //   bmpow_host_packets.hip packet framing in front of the intake: checksums, verdicts (include/bmpow_packets.h)
 //   bmpow_host_inv.hip     the inventory sets behind them: have and missing on the device (include/bmpow_inv.h)
+//   bmpow_host_proc.hip    the object processor's queue: acks, getpubkeys, onionpeers, routes (include/bmpow_proc.h)
 //   bmpow_host_sig.hip     ECDSA signature verification of received objects (include/bmpow_sig.h)
 //   bmpow_host_send.hip    public keys, signatures and ECIES encryption of outgoing objects (include/bmpow_send.h)
 //   bmpow_host_seal.hip    the seal and CBC kernels' round trip;   bmpow_host_tx.hip  outgoing objects in one call
@@ -53,6 +54,7 @@ void free_shards() {
   intake_release_shards();
   packets_release_shards();
   inv_release_shards();
+  proc_release_shards();
   for (Shard& s : g_shards) {
     s.ev0.reset();
     s.ev1.reset();

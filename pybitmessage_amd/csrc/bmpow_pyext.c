@@ -1,5 +1,6 @@
 /* bmpow_pyext.c -- CPython marshalling for the batched receive-side verification
- * (pybitmessage_amd.verify.isProofOfWorkSufficient_batch) and object intake (pybitmessage_amd.intake.check_objects).
+ * (pybitmessage_amd.verify.isProofOfWorkSufficient_batch), object intake (pybitmessage_amd.intake.check_objects) and
+ * the object processor's dispatch (pybitmessage_amd.processor.Dispatcher.dispatch).
  *
  * The reference checks each received object with protocol.isProofOfWorkSufficient
  * (src/protocol.py:258-286) as it arrives; the batched path hands a whole inventory flood to
@@ -174,6 +175,58 @@ static PyObject *intake_list(PyObject *self, PyObject *args) {
     return PyLong_FromLong(rc);
 }
 
+typedef int (*proc_batch_fn)(void *d, size_t n, const uint8_t *const *objs, const uint64_t *lens, const uint32_t *types,
+                             const void *params, void *out);
+
+/* proc_list(fn_address, dispatcher_address, objects: list of bytes, types_address, params_address, out_address) -> rc
+ * bmpow_proc_batch (include/bmpow_proc.h) over a list of bytes: the same walk as intake_list, then the call with
+ * the GIL released.  types_address: len(objects) uint32; params_address: a bmpow_proc_params; out_address: room
+ * for len(objects) bmpow_proc_rec (pybitmessage_amd.processor passes numpy arrays').  TypeError when an item is
+ * not a bytes object (the caller converts those first). */
+static PyObject *proc_list(PyObject *self, PyObject *args) {
+    unsigned long long fn_addr, d_addr, types_addr, prm_addr, out_addr;
+    PyObject *list;
+    (void)self;
+    if (!PyArg_ParseTuple(args, "KKO!KKK", &fn_addr, &d_addr, &PyList_Type, &list, &types_addr, &prm_addr, &out_addr))
+        return NULL;
+    const Py_ssize_t n = PyList_GET_SIZE(list);
+    scratch_t own;
+    memset(&own, 0, sizeof(own));
+    scratch_t *sc = g_scratch.busy ? &own : &g_scratch;
+    if (scratch_reserve(sc, (size_t)(n ? n : 1)) < 0) {
+        scratch_free(&own);
+        return PyErr_NoMemory();
+    }
+    sc->busy = 1;
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        if (i + 16 < n) __builtin_prefetch(PyList_GET_ITEM(list, i + 16), 1);
+        PyObject *o = PyList_GET_ITEM(list, i);
+        if (!PyBytes_CheckExact(o)) {
+            for (Py_ssize_t j = 0; j < i; ++j) Py_DECREF(sc->held[j]);
+            sc->busy = 0;
+            scratch_free(&own);
+            return PyErr_Format(PyExc_TypeError, "object %zd is not bytes", i);
+        }
+        Py_INCREF(o);
+        sc->held[i] = o;
+        sc->ptrs[i] = (const uint8_t *)PyBytes_AS_STRING(o);
+        sc->lens[i] = (uint64_t)PyBytes_GET_SIZE(o);
+    }
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = ((proc_batch_fn)(uintptr_t)fn_addr)((void *)(uintptr_t)d_addr, (size_t)n, sc->ptrs, sc->lens,
+                                             (const uint32_t *)(uintptr_t)types_addr, (const void *)(uintptr_t)prm_addr,
+                                             (void *)(uintptr_t)out_addr);
+    Py_END_ALLOW_THREADS
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        if (i + 16 < n) __builtin_prefetch(sc->held[i + 16], 1);
+        Py_DECREF(sc->held[i]);
+    }
+    sc->busy = 0;
+    scratch_free(&own);
+    return PyLong_FromLong(rc);
+}
+
 /* verdicts(ok: bytes of 0/1) -> list of bool.  numpy's bool tolist() costs ~16 ns per object (8 ms for a
  * 500k flood, a fifth of the whole call); the two singletons referenced directly cost a few ns. */
 static PyObject *verdicts(PyObject *self, PyObject *arg) {
@@ -202,6 +255,7 @@ static PyMethodDef methods[] = {
     {"verify_list", verify_list, METH_VARARGS, "bmpow_verify_batch_ptrs over a list of bytes (see module doc)"},
     {"verdicts", verdicts, METH_O, "bytes of 0/1 -> list of bool"},
     {"intake_list", intake_list, METH_VARARGS, "bmpow_intake_batch over a list of bytes (see module doc)"},
+    {"proc_list", proc_list, METH_VARARGS, "bmpow_proc_batch over a list of bytes (see module doc)"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef module = {PyModuleDef_HEAD_INIT, "_bmpow_fast",

@@ -1,6 +1,6 @@
 """The inventory sets on the GPU (``pybitmessage_amd.inventory``) against a plain dict model written here, and
 against the reference-made fixture ``tests/golden/inv_kats.json`` (tests/golden/make_inv_golden.py): the golden
-packets through ``check_invs``, constructed probe clusters, equal keys racing inside one call, growth, sweep and
+packets through ``check_invs``, items at every byte residue of the upload and on its last byte, constructed probe clusters, equal keys racing inside one call, growth, sweep and
 list, ``admit`` behind a real intake and behind ``check_buffers``, and a set's life across a re-selection.
 Every malformed input here is a defined status: nothing provokes a fault."""
 import hashlib
@@ -15,6 +15,7 @@ from pybitmessage_amd import _lib, intake, inventory, packets
 from pybitmessage_amd.inventory import ABSENT, ADDED, DUP, PRESENT
 from tests.golden.make_intake_golden import regen as regen_object
 from tests.golden.make_inv_golden import item, regen_payload, runs_to_ids
+from tests.test_inv import RESIDUE_FORMS, residue_case, residue_expected, residue_layout
 
 pytestmark = pytest.mark.gpu
 
@@ -142,6 +143,54 @@ def test_golden_cases_through_check_invs(gpulib, kats):
                 assert res.item(int(j)) in m_missing
         big = next(c for c in kats['cases'] if c['name'] == 'inv_50000')
         assert len(runs_to_ids(big['missing_final_runs'])) == 50000 - 107
+
+
+# ---- 1b. items at every residue of the upload ----
+
+def test_items_at_every_residue_and_the_uploads_last_byte(gpulib):
+    """``ivf::load_key`` on the device at every ``off mod 8`` (the aligned branch, the funnel with its fifth word)
+    and ``load_word``'s byte-by-byte read of the upload's partial last word, in lookup, claim and finalize: per
+    case one ``check_invs`` call of tests/test_inv.py's ``residue_case`` -- A (in ``have``) at residue r, and B
+    twice, at residue 1 and at residue r where it ends the upload, so whichever row takes the slot the other
+    compares with an input row at another residue.  8 residues x 5 count forms x (B new | B in ``missing``)."""
+    now = 1700000000
+    layouts = {form[0]: set() for form in RESIDUE_FORMS}
+    with inventory.InventorySet(64, seed=41) as have, inventory.InventorySet(64, seed=42) as missing:
+        n = 0
+        for preloaded in (False, True):
+            for form in RESIDUE_FORMS:
+                for r in range(8):
+                    a, b, n = item(90000 + 2 * n), item(90001 + 2 * n), n + 1
+                    payloads, kinds = residue_case(r, form, a, b)
+                    at, end = residue_layout(payloads, kinds)
+                    assert at == end == r
+                    layouts[form[0]].add(at)
+                    have.clear(), missing.clear()
+                    have.add([a], expires=now + 5, stream=1)
+                    m_missing = {}
+                    if preloaded:
+                        missing.add([b], expires=1)
+                        m_missing[b] = 1
+                    want = model_check_invs(payloads, kinds, {a}, m_missing, now)
+                    want_pkts, want_states = residue_expected(form, preloaded)
+                    assert [(s, k) for s, _, k in want[0]] == want_pkts and want[1] == want_states
+                    res = inventory.check_invs(payloads, kinds, have, missing, now)
+                    where = (form[0], r, preloaded)
+                    assert res.status.tolist() == [s for s, _ in want_pkts], where
+                    assert res.item_state.tolist() == want[1] and res.item_first.tolist() == want[2], where
+                    check_result(res, want)
+                    assert [res.item(j) for j in range(len(res))] == ([b, a, b, b''][:len(res)]), where
+                    # the key finalize stored is the right 32 bytes, under the value the model holds
+                    assert set_keys(missing) == sorted(m_missing) == [b], where
+                    found, vals = missing.contains([b, a], values=True)
+                    assert found.tolist() == [True, False] and int(vals['expires'][0]) == m_missing[b], where
+                    assert m_missing[b] == (1 if preloaded else now)
+                    assert set_keys(have, 1) == [a] and len(have) == 1 and len(missing) == 1
+                    if kinds[1] == inventory.GETDATA:  # the getdata itself left `missing` alone: T came with the filler
+                        alone = inventory.check_invs(payloads[1:], kinds[1:], have, missing, now)
+                        assert alone.item_state.tolist() == want[1][1:] and set_keys(missing) == [b], where
+                        assert int(missing.contains([b], values=True)[1]['expires'][0]) == m_missing[b]
+    assert all(seen == set(range(8)) for seen in layouts.values()), layouts
 
 
 # ---- 2. constructed clusters ----

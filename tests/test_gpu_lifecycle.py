@@ -5,9 +5,10 @@ memory left behind.  Small leaks are the native owner test's job (tests/native/o
 table (64 MiB) or a verification staging chunk's pool left behind shows here.
 
 The first test re-runs PoW, the probe, the verification and the address search in each layout.  The second
-runs every crypto entry point (tests/workloads.py: the signature, send and outgoing units read the comb table
-the address search builds, the others keep grow-only buffers per call family) in each layout of a cycle run
-three times.  The third re-selects the devices under a live PowService: what the service holds was built for
+runs every crypto and network-side entry point (tests/workloads.py: the signature, send and outgoing units read
+the comb table the address search builds, the others -- packet framing, the inventory sets and the dispatcher
+among them -- keep grow-only buffers per call family, and a set or a dispatcher is made for the layout it runs
+in) in each layout of a cycle run three times.  The third re-selects the devices under a live PowService: what the service holds was built for
 the old shard set, and the library must refuse to step it (the set's generation, not its size, decides).
 Run on an MI355X."""
 import ctypes

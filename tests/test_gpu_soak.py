@@ -14,7 +14,9 @@ layout changing between phases -- the way a long-running node uses the library.
 * one thread cycles through the crypto entry points (tests/workloads.py: intake.check_objects, the POW values,
   signatures.verify_batch_digest, ecies.decrypt_batch and aes_cbc_batch, addresses.derive_batch, the
   receive.open_* calls, sender.sign_batch / encrypt_batch, outgoing.build_objects, the address search and
-  addressgen.pubkeys), each result byte-equal to its idle baseline, which workloads.baseline() holds against
+  addressgen.pubkeys, and the network side: packets.check_buffers / check_acks, inventory.check_invs / admit on
+  sets made afresh in every run, Dispatcher.dispatch), each result byte-equal to its idle baseline, which
+  workloads.baseline() holds against
   the reference-made fixtures -- their call-scoped device buffers are allocated and freed on shard 0's
   stream while the engine launches on it.
 

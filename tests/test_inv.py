@@ -138,6 +138,85 @@ def test_slot_is_stable_under_a_seed_and_differs_across_seeds():
     assert inventory.slot_of(7, 0, keys[0]) == 0 and inventory.slot_of(7, 31, keys[0]) == 0  # out of range
 
 
+# ---- items at every byte residue of the upload (the device half is in tests/test_gpu_inv.py) ----
+
+#: the count in front of the probe's two items, and the kind the probe is judged as: (name, count bytes, kind)
+RESIDUE_FORMS = (
+    ('two', b'\x02', inventory.INV),
+    ('announces_256', b'\xfd\x01\x00', inventory.INV),                      # two full items, then the first empty one
+    ('announces_65536_inv', b'\xfe\x00\x01\x00\x00', inventory.INV),        # TOO_MANY: none of its items is processed
+    ('announces_65536_getdata', b'\xfe\x00\x01\x00\x00', inventory.GETDATA),
+    ('announces_2_32_getdata', b'\xff\x00\x00\x00\x01\x00\x00\x00\x00', inventory.GETDATA),  # no bound on a getdata
+)
+RESIDUE_ITEM_OFFSETS = {1, 3, 5, 9}
+
+
+def residue_case(r, form, a, b):
+    """``(payloads, kinds)`` of one ``check_invs`` call that puts 32-byte items at chosen residues of the upload
+    (the payloads go up back to back).  The filler, an ``inv`` of one item ``T == b`` and a pad behind it that is
+    not looked at, ends where the probe's first item ``a`` starts at an offset congruent to ``r`` mod 8; the probe,
+    ``count + a + b``, is the last payload, so ``b``'s last byte is the upload's last byte and the upload's length
+    is congruent to ``r`` too: its last word is partial for r in 1..7.  ``b`` is carried twice, at residue 1 in the
+    filler and at residue ``r`` in the probe."""
+    _name, count, kind = form
+    pad = bytes(0xa0 + i for i in range((r - len(count) - 33) % 8))
+    return [b'\x01' + b + pad, count + a + b], [inventory.INV, kind]
+
+
+def residue_layout(payloads, kinds):
+    """``(upload offset of the probe's first item % 8, upload length % 8)``, from the walk and the lengths."""
+    filler, probe = payloads
+    at = len(filler) + inventory.walk(probe, kinds[1]).item_offset
+    return at % 8, (len(filler) + len(probe)) % 8
+
+
+def residue_expected(form, preloaded):
+    """Per packet ``(status, n_items)`` and the item states of a residue case with ``a`` in ``have`` and ``b`` in
+    neither set, or (``preloaded``) in ``missing``: the filler's T, then A, B and the first empty item."""
+    _name, count, kind = form
+    first = inventory.KNOWN if preloaded else inventory.NEW
+    if kind == inventory.GETDATA:
+        states = [first, inventory.HAVE, inventory.NOT_HAVE, inventory.SHORT]
+    elif count == b'\xfe\x00\x01\x00\x00':
+        return [(inventory.OK, 1), (inventory.TOO_MANY, 0)], [first]
+    else:
+        states = [first, inventory.HAVE, inventory.KNOWN if preloaded else inventory.NEW_AGAIN]
+        states += [inventory.SHORT] if count != b'\x02' else []
+    return [(inventory.OK, 1), (inventory.OK, len(states) - 1)], states
+
+
+def test_residue_cases_cover_every_residue_and_the_model_judges_them():
+    """The construction of the device test ``test_items_at_every_residue_and_the_uploads_last_byte``, checked
+    without a device: for every count form the probe's first item meets all eight residues and the upload ends at
+    the same residue, the host walk reads the probe as the model's walk does, and the model gives the states the
+    construction is meant to provoke."""
+    from tests.test_gpu_inv import model_check_invs, py_walk
+    assert {len(count) for _, count, _ in RESIDUE_FORMS} == RESIDUE_ITEM_OFFSETS
+    a, b = item(90000), item(90001)
+    for form in RESIDUE_FORMS:
+        seen = set()
+        for r in range(8):
+            payloads, kinds = residue_case(r, form, a, b)
+            at, end = residue_layout(payloads, kinds)
+            assert at == end == r, (form[0], r)
+            seen.add(at)
+            # B twice in one call: at residue 1 in the filler, at residue r in the probe, ending the upload
+            assert payloads[0][1:33] == b and payloads[1][-32:] == b and len(payloads[0]) % 8 == (r - len(form[1])) % 8
+            for p, k in zip(payloads, kinds):
+                got = inventory.walk(p, k)
+                status, items = py_walk(p, k, False)
+                assert (got.status, got.n_items) == (status, len(items)), (form[0], r)
+            for preloaded in (False, True):
+                m_missing = {b: 1} if preloaded else {}
+                pkts, states, firsts = model_check_invs(payloads, kinds, {a}, m_missing, 1700000000)
+                want_pkts, want_states = residue_expected(form, preloaded)
+                assert [(s, n) for s, _, n in pkts] == want_pkts and states == want_states, (form[0], r, preloaded)
+                again = [j for j, s in enumerate(states) if s == inventory.NEW_AGAIN]
+                assert firsts == [0 if j in again else j for j in range(len(states))]
+                assert m_missing == {b: 1 if preloaded else 1700000000}
+        assert seen == set(range(8)), form[0]
+
+
 #: bm_command_object behind checkAlreadyHave (src/network/bmproto.py:401-435), status by status: is
 #: ``Inventory()[hash] = ...`` (:431) reached?  (without acceptmismatch, with it)
 STORE_TABLE = {

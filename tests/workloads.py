@@ -11,7 +11,10 @@ imported, never copied -- or, where that test compares with the fixture directly
 later comparison -- beside a busy service, after an abort, under another shard layout -- is byte equality
 with that.  The chain is fixture -> existing checker -> baseline bytes -> equality; nothing here invents an
 expectation.  No workload reads a ``*_stats()`` delta: the counters are process-wide and mean nothing while
-other threads call the library.
+other threads call the library.  A workload that needs an object bound to the device selection (an
+``InventorySet``, a ``Dispatcher``) makes it inside ``run()`` in a ``with`` block and never keeps it: the
+workloads run across re-selections and under an abort that may land between two of their calls.  Beside a
+busy service every library call waits for the lock, so a workload makes few of them.
 """
 import hashlib
 import itertools
@@ -310,7 +313,177 @@ def _aes():
     return Workload('aes', run, check, lambda res: _canon([res[0], res[1]]))
 
 
-_MAKERS = (_intake, _verify, _sig, _ecies, _ident, _rx, _rxobj, _rxsealed, _send, _tx, _addr, _aes)
+# ------------------------------------------------------------------ the network side
+def _packets():
+    from pybitmessage_amd import packets
+    from tests import test_gpu_packets as t
+    kats = load_golden('packet_kats.json')
+    intake_objects = _plain(t.intake_objects)(load_golden)
+    groups = {}
+    for case in kats['connections']:
+        groups.setdefault((case['now'], tuple(case['streams'])), []).append(case)
+    calls = [(now, streams, [t.regen_buffer(c, intake_objects) for c in cases], [c['established'] for c in cases],
+              [c['datagram'] for c in cases]) for (now, streams), cases in groups.items()]
+    acks = [t.regen_buffer(a, intake_objects) for a in kats['acks']]
+
+    def run():
+        framed = [packets.check_buffers(bufs, established, datagram, streams=streams, now=now)
+                  for now, streams, bufs, established, datagram in calls]
+        return framed, packets.check_acks(acks, now=t.NOW)
+
+    def canon(res):
+        framed, (valid, recs) = res
+        return _canon([[r.records, r.consumed, r.close] for r in framed] + [valid, recs.records])
+
+    def check(res):
+        # test_the_fixture_is_reproduced_record_for_record and test_check_acks_agrees_... are the checkers: they
+        # make these very calls (and one buffer alone, and the acks once more through receive.check_opened_acks),
+        # so they run with both entry points recording what they returned, and what they accepted is these bytes
+        seen, seen_acks, real, real_acks = [], [], packets.check_buffers, packets.check_acks
+
+        def recording(*a, **kw):
+            seen.append(real(*a, **kw))
+            return seen[-1]
+
+        def recording_acks(*a, **kw):
+            seen_acks.append(real_acks(*a, **kw))
+            return seen_acks[-1]
+        packets.check_buffers, packets.check_acks = recording, recording_acks
+        try:
+            t.test_the_fixture_is_reproduced_record_for_record(None, kats, intake_objects)
+            t.test_check_acks_agrees_with_the_host_check_on_every_fixture_ack(None, kats, intake_objects)
+        finally:
+            packets.check_buffers, packets.check_acks = real, real_acks
+        assert len(seen) == len(calls) + 1 and len(seen_acks) == 2
+        assert canon((seen[:len(calls)], seen_acks[0])) == canon(res)
+    return Workload('packets', run, check, canon)
+
+
+def _set_keys(s, streams, cap):
+    """The set's keys of the given streams (at most ``cap`` of each) as one (m, 32) array in byte order: one
+    library call per stream."""
+    keys = np.concatenate([s.unexpired_hashes_by_stream(stream, 0, cap=cap)[0] for stream in streams])
+    words = np.ascontiguousarray(keys).view('>u8').reshape(-1, 4)
+    return keys[np.lexsort((words[:, 3], words[:, 2], words[:, 1], words[:, 0]))]
+
+
+def _inv():
+    from pybitmessage_amd import intake, inventory
+    from tests import test_gpu_inv as t
+    kats = load_golden('inv_kats.json')
+    intake_kats = load_golden('intake_kats.json')
+    now = 1700000000
+    # Every golden case's packets, in the fixture's order, as one check_invs call per dandelion setting (the flag
+    # is the call's) against the union of the cases' initial sets: beside a busy service every library call waits
+    # for the lock, so a call per case -- and the two clears, two adds and two lists around it -- is what
+    # tests/test_gpu_inv.py does once, not what a workload repeats.  The cases then meet inside a call (one case's
+    # announcement is another's NEW_AGAIN), which the model follows.
+    cases = kats['cases']
+    flood = []
+    for dandelion in (False, True):
+        mine = [c for c in cases if c['dandelion'] == dandelion]
+        pkts = [p for c in mine for p in c['packets']]
+        flood.append((dandelion, sorted(set(t.item(k) for c in mine for k in t.runs_to_ids(c['have']))),
+                      sorted(set(t.item(k) for c in mine for k in t.runs_to_ids(c['missing']))),
+                      [t.regen_payload(p) for p in pkts], [t.KIND[p['kind']] for p in pkts]))
+    most = sum(len(p) // 32 + 1 for f in flood for p in f[3]) + sum(len(f[2]) for f in flood)
+    # the groups, the doubled batches and the announced hashes of test_admit_behind_a_real_intake
+    groups = {}
+    for k in intake_kats['kats']:
+        c = k['checks'][0]
+        groups.setdefault((c['now'], tuple(c['streams'])), []).append(k)
+    groups = [(key, [t.regen_object(k) for k in group] * 2) for key, group in sorted(groups.items())]
+    announced = sorted(set(bytes.fromhex(k['fields']['inv']) for k in intake_kats['kats'] if k['fields'] is not None))
+    announced += [t.item(60000 + k) for k in range(5)]
+    stored_streams = sorted(set(min(s, 0xffffffff) for (_, streams), _ in groups for s in streams))
+
+    def run():
+        judged, admitted = [], []
+        with inventory.InventorySet(64, seed=11) as have, inventory.InventorySet(64, seed=12) as missing:
+            for dandelion, have0, missing0, payloads, kinds in flood:
+                have.add(have0, expires=now + 5, stream=1)
+                missing.add(missing0, expires=1)
+                res = inventory.check_invs(payloads, kinds, have, missing, now, dandelion=dandelion)
+                judged.append((res, _set_keys(missing, (0,), most), _set_keys(have, (1,), 4096)))
+                have.clear(), missing.clear()
+            missing.add(announced, expires=1)
+            for (at, streams), objs in groups:
+                recs = intake.check_objects(objs, streams=streams, now=at)
+                admitted.append((recs, inventory.admit(recs, have, missing)))
+            return judged, admitted, _set_keys(missing, (0,), 4096), _set_keys(have, stored_streams, 4096)
+
+    def canon(res):
+        judged, admitted, missing_keys, have_keys = res
+        return _canon([[r.item_state, r.item_first, r.packets, m, h] for r, m, h in judged] +
+                      [[recs.records, a.already, a.state] for recs, a in admitted] + [missing_keys, have_keys])
+
+    def rows(keys):
+        return [bytes(k) for k in keys]
+
+    def check(res):  # the models and comparisons of tests/test_gpu_inv.py, on what run() kept of the sets
+        judged, admitted, missing_keys, have_keys = res
+        assert len(judged) == 2 and len(admitted) == len(groups)
+        for case in cases:  # the model restates the reference case by case, as in test_golden_cases_through_check_invs
+            m_missing = dict.fromkeys([t.item(k) for k in t.runs_to_ids(case['missing'])], 1)
+            t.model_check_invs([t.regen_payload(p) for p in case['packets']], [t.KIND[p['kind']] for p in case['packets']],
+                               set(t.item(k) for k in t.runs_to_ids(case['have'])), m_missing, now, case['dandelion'])
+            final = sorted([t.item(k) for k in t.runs_to_ids(case['missing_final_runs'])] +
+                           [bytes.fromhex(x) for x in case['missing_final_other'] if len(x) == 64])
+            assert sorted(m_missing) == final, case['name']
+        seen, statuses = set(), set()
+        for (dandelion, have0, missing0, payloads, kinds), (r, m, h) in zip(flood, judged):  # ... and the device the model
+            m_missing = dict.fromkeys(missing0, 1)
+            t.check_result(r, t.model_check_invs(payloads, kinds, set(have0), m_missing, now, dandelion))
+            assert rows(m) == sorted(m_missing) and rows(h) == have0
+            seen.update(r.item_state.tolist())
+            statuses.update(r.status.tolist())
+        assert seen == {inventory.NOT_HAVE, inventory.HAVE, inventory.KNOWN, inventory.NEW, inventory.NEW_AGAIN,
+                        inventory.SHORT}
+        assert statuses == {inventory.OK, inventory.MALFORMED, inventory.TOO_MANY, inventory.IGNORED}
+        m_have, m_missing = set(), dict.fromkeys(announced, 1)
+        for (_, objs), (recs, a) in zip(groups, admitted):
+            assert len(recs) == len(objs)
+            invs = [recs.inventory_hash(i) for i in range(len(recs))]
+            want_already, want_state = t.model_admit(recs.status.tolist(), invs, m_have, m_missing)
+            assert a.already.tolist() == want_already and a.state.tolist() == want_state
+        assert rows(missing_keys) == sorted(m_missing) and rows(have_keys) == sorted(m_have)
+        assert len(m_have) > 3 and 5 <= len(m_missing) < len(announced)
+    return Workload('inv', run, check, canon)
+
+
+def _proc():
+    from tests import test_gpu_proc as t
+    from tests.proc_expect import objects
+    kats = load_golden('proc_kats.json')
+    objs, types = objects(kats)
+    watched = [bytes.fromhex(k) for k in kats['watch']]
+
+    def run():
+        with t.fixture_dispatcher(kats) as d:
+            res = d.dispatch(objs, types, now=kats['now'], rows_per_launch=16)
+            n = len(d)
+            # the keys still watched, asked in one call (every call waits for the library's lock): the dispatcher
+            # is closed behind this line, so taking them out is as good as asking
+            left = d.unwatch(watched)
+            return res, sorted(k for k, there in zip(kats['watch'], left) if there), n
+
+    class Left(object):  # what check_fixture asks of the dispatcher, from what run() kept of it
+        def __init__(self, left, n):
+            self.left, self.n = left, n
+
+        def watching(self, key):
+            return key.hex() in self.left
+
+        def __len__(self):
+            return self.n
+
+    def check(res):
+        t.check_fixture(kats, Left(res[1], res[2]), res[0])
+        assert len(res[0]) == len(objs)
+    return Workload('proc', run, check, lambda res: _canon([res[0].records, res[1], res[2]]))
+
+
+_MAKERS = (_intake, _verify, _sig, _ecies, _ident, _rx, _rxobj, _rxsealed, _send, _tx, _addr, _aes, _packets, _inv, _proc)
 _lock = threading.Lock()
 _workloads = None
 _baseline = None
